@@ -27,8 +27,14 @@ sharded over the ranks (dist.sharded_decode's layout), slabs gathered to rank 0.
 Weights and inputs are synthetic and seeded (confild_amd.synth); there is no
 network access for checkpoints.  Rank 0 prints ONE JSON line with the driver
 contract, a ``roofline`` object for the dominant kernel (the CNF decoder, HIP
-events on its stream), a ``roofline_unet`` object for the U-Net forward, and a
-``cpu_baseline`` (the oracle on this host's cores, rank 0, N = 1).
+events on its stream) and a ``roofline_unet`` object for the U-Net forward, both
+from the events of the timed steps themselves.
+
+A plain run sets up, warms up, times ``--steps`` steps and prints that line.
+``--full`` adds the legs that take runs of their own: the ``cpu_baseline`` (the
+oracle on this host's cores, rank 0, N = 1) and, on several GPUs, the nested
+``strong`` point of config B.  ``--dump-outputs DIR`` writes what the last timed
+step returned as ``DIR/<name>.npy`` (dump_outputs).
 """
 from __future__ import annotations
 
@@ -124,6 +130,28 @@ def measured_mfma_util(mode, cus=None):
             out["clock_condition"] = cond
             out["clock_source"] = f"profiles/{CLOCK_RECORD}"
     return out
+
+
+DUMP_BUDGET = 48 << 20   # bytes that --dump-outputs writes at most (all arrays together)
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: what the timed path returned from its last step, one
+    DIR/<name>.npy (float32) per array.  An array above its share of DUMP_BUDGET
+    is cut to a fixed sample first: sorted indices along its longest axis, drawn
+    from numpy's default_rng(0) -- the same indices in every run and every build,
+    as the seeded inputs are."""
+    os.makedirs(dirname, exist_ok=True)
+    budget = DUMP_BUDGET // len(arrays)
+    for name, t in arrays.items():
+        t = t.detach()
+        nbytes = t.numel() * 4
+        if nbytes > budget:
+            ax = max(range(t.dim()), key=lambda i: t.shape[i])
+            keep = max(1, t.shape[ax] * budget // nbytes)
+            idx = np.sort(np.random.default_rng(0).choice(t.shape[ax], keep, replace=False))
+            t = t.index_select(ax, torch.from_numpy(idx).to(t.device))
+        np.save(os.path.join(dirname, name + ".npy"), t.to(torch.float32).cpu().numpy())
 
 
 def siren_flops_per_pair(d, L, c, nh, H):
@@ -541,6 +569,8 @@ def main_uncond(args, rank, world, dev):
     model.check_finite(dev)
     if rank == 0:
         assert torch.isfinite(out).all().item(), "non-finite output"
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"fields": out})
         mode = nf.compute_mode(dev)
         kname, peak, peak_basis, _ = ROOFLINE[mode]
         flops = batch * Sz * N * siren_flops_per_pair(**sc)
@@ -570,7 +600,7 @@ def main_uncond(args, rank, world, dev):
                                  "f16 dense MFMA peak / 3 (split-f16 convolutions)",
                                  "unit": "TFLOP/s", "frac": ua / upeak, "flops": uf, "ms": unet_ms,
                                  "ms_per_forward": unet_ms / nsteps},
-               "cpu_baseline": None if args.no_cpu_baseline or world > 1 else cpu_baseline(args.config),
+               "cpu_baseline": cpu_baseline(args.config) if want_cpu_baseline(args, world) else None,
                "rccl_ranks": world}
         print(json.dumps(rec), flush=True)
     if world > 1:
@@ -879,6 +909,11 @@ def cpu_baseline(config):
     return out
 
 
+def want_cpu_baseline(args, world):
+    """The CPU baseline is a run of its own (the oracle on the host): --full only."""
+    return args.full and not args.no_cpu_baseline and world == 1
+
+
 # ---------------------------------------------------------------------------
 def main():
     ap = argparse.ArgumentParser()
@@ -894,7 +929,13 @@ def main():
                     help="A / B / D / E / Case4: the U-Net planner's nominal batch (-1: the config's; 0: 8)")
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak")
     ap.add_argument("--no-gather", action="store_true", help="keep decoded fields on their ranks")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the CPU baseline and, on several "
+                         "GPUs, config B's strong-scaling point")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy (float32; "
+                         "a fixed seeded sample of an output above 48 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--no-pipeline", action="store_true",
                     help="B: sample and decode each batch in sequence on the whole chip (the default pipelines "
                          "from 4 timed steps)")
@@ -1049,11 +1090,11 @@ def main():
     achieved = flops / (dec_ms / 1e3) / 1e12
     if rank == 0 and out is not None:
         assert torch.isfinite(out).all().item(), "non-finite output"
-    strong = strong_point() if args.config == "B" and world > 1 and args.scaling == "weak" else None
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"fields": out})
+    strong = strong_point() if args.full and args.config == "B" and world > 1 and args.scaling == "weak" else None
     if rank == 0:
-        cpu = None
-        if not args.no_cpu_baseline and world == 1:
-            cpu = cpu_baseline(args.config)
+        cpu = cpu_baseline(args.config) if want_cpu_baseline(args, world) else None
         par = (f"dp{world} ({f'{count} samples per GPU' if args.scaling == 'weak' else 'global batch 8 split'}"
                f"{', fields gathered to rank 0' if gather else ''})") if args.config == "B" else \
             f"coord-sharded over {world} GPU(s){', slabs gathered to rank 0' if gather else ''}"
@@ -1177,6 +1218,8 @@ def main_dps(args, rank, world, dev):
     barrier(dev, world)
     elapsed = max_over_ranks(time.perf_counter() - t0, dev, world)
     assert torch.isfinite(out).all().item(), "non-finite output"
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"latents": out})
     o["model"].check_finite(dev)
     steps_total = timed * args.steps
     its = steps_total * batch * world / elapsed
@@ -1216,7 +1259,7 @@ def main_dps(args, rank, world, dev):
                             "flops_per_chain_step": per_chain,
                             "flops_split": {"unet_forward": sum(uf.values()), "unet_input_vjp": uf["conv"] + 2 * uf["attn"],
                                             "siren_forward": sf["forward"], "siren_backward": sf["backward"]}},
-               "cpu_baseline": None if args.no_cpu_baseline or world > 1 else cpu_baseline(args.config),
+               "cpu_baseline": cpu_baseline(args.config) if want_cpu_baseline(args, world) else None,
                "rccl_ranks": world}
         print(json.dumps(rec), flush=True)
     if world > 1:

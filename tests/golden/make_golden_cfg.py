@@ -18,12 +18,12 @@ Fixtures
   * golden_trajB.npz  -- config B: the full 256-step DDPM reverse loop
     (U/src/gaussian_diffusion.py:441-535, respacing "256") of the 64x64 U-Net
     at B = 1, samples at checkpoint steps + the final latent;
-  * golden_trajE.npz  -- config E: two 20-step segments (indices 999..980 and
+  * golden_trajE.npz, golden_trajE_19.npz -- config E: two 20-step segments (indices 999..980 and
     19..0) of the 1000-step DDPM loop of the 128x128 default-mult U-Net at
     B = 1 through the reference's p_sample, sample and x0_hat per step;
   * golden_trajE100.npz -- config E: 100 consecutive steps (indices 599..500)
     of the same loop, sample and x0_hat every 10 steps and at the end;
-  * golden_case4steps.npz -- the real Case4 loop: 10 consecutive DDPM + 'ps'
+  * golden_case4steps.npz, golden_case4steps_final.npz -- the real Case4 loop: 10 consecutive DDPM + 'ps'
     steps (indices 500..491) at 384^2: per step the residual norm, image and
     x0_hat on a 4x-strided subgrid and whole-image checksums; the final image;
   * golden_cfgA.npz   -- config A end to end: the DDIM-50 loop
@@ -156,7 +156,12 @@ def gen_trajE():
         out_arrays[f"samples{start}"] = np.stack([samples[k] for k in keep])
         out_arrays[f"pred_xstart{start}"] = np.stack([x0s[k] for k in keep])
     print(f"trajE: {sum(n for _, n in c['segments'])} steps in {time.time() - t0:.1f} s")
-    _save("golden_trajE.npz", keep=np.array(c["keep"], dtype=np.int64), **out_arrays)
+    # one file per segment (each under the 1 MiB limit for a committed file)
+    first, rest = c["segments"][0][0], [s for s, _ in c["segments"][1:]]
+    _save("golden_trajE.npz", keep=np.array(c["keep"], dtype=np.int64),
+          **{k: v for k, v in out_arrays.items() if k.endswith(str(first))})
+    for s in rest:
+        _save(f"golden_trajE_{s}.npz", **{k: v for k, v in out_arrays.items() if k.endswith(str(s))})
 
 
 def gen_trajE100():
@@ -400,7 +405,8 @@ def gen_case4steps():
     # compact: every step on a 4x-strided 96x96 subgrid, whole-image checksums, the final image in full
     _save("golden_case4steps.npz", dists=np.array(dists), img_sub=imgs[..., ::4, ::4].copy(),
           x0_sub=x0s[..., ::4, ::4].copy(), img_sum=imgs.astype(np.float64).sum(axis=(1, 2, 3, 4)),
-          img_absmax=np.abs(imgs).max(axis=(1, 2, 3, 4)), img_final=imgs[-1])
+          img_absmax=np.abs(imgs).max(axis=(1, 2, 3, 4)))
+    _save("golden_case4steps_final.npz", img_final=imgs[-1])   # apart: the 1 MiB limit for a committed file
 
 
 # ---------------------------------------------------------------------------

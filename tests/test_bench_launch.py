@@ -2,7 +2,8 @@
 driver's `python bench.py --gpus N` must yield N RCCL ranks): each child gets the
 torchrun environment (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR), and the
 parent has not initialised HIP when it starts them (CPU test, --launch-check
-stops every rank before any GPU call)."""
+stops every rank before any GPU call).  Also the host side of --dump-outputs and
+of --full (CPU tests of bench.dump_outputs and bench.want_cpu_baseline)."""
 import json
 import os
 import subprocess
@@ -43,3 +44,38 @@ def test_wait_ranks_fails_fast_and_stops_the_others():
     assert time.time() - t0 < 60 and hang.poll() is not None
     ok = [subprocess.Popen([sys.executable, "-c", "pass"]) for _ in range(2)]
     assert bench.wait_ranks(ok, time.sleep) == 0
+
+
+def test_dump_outputs_writes_float32_and_a_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs: a small array is written whole as float32; one above the
+    budget is cut along its longest axis to the same seeded, sorted indices on
+    every call, and what is written stays within the budget."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    small = torch.arange(24, dtype=torch.float64).reshape(2, 3, 4)
+    bench.dump_outputs(str(tmp_path / "a"), {"latents": small})
+    got = np.load(tmp_path / "a" / "latents.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, small.numpy())
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 4000)
+    big = torch.arange(3 * 1001 * 2, dtype=torch.float32).reshape(3, 1001, 2)
+    bench.dump_outputs(str(tmp_path / "b"), {"fields": big})
+    bench.dump_outputs(str(tmp_path / "c"), {"fields": big})
+    b, c = np.load(tmp_path / "b" / "fields.npy"), np.load(tmp_path / "c" / "fields.npy")
+    assert np.array_equal(b, c) and b.dtype == np.float32 and b.nbytes <= 4000
+    assert b.shape == (3, 4000 * 1001 // big.numel() // 4, 2)
+    idx = (b[0, :, 0] // 2).astype(int)            # the rows of `big` that were kept
+    assert np.all(np.diff(idx) > 0) and np.array_equal(b, big.numpy()[:, idx])
+
+
+def test_plain_run_skips_the_cpu_baseline():
+    """The CPU baseline runs with --full only (and --no-cpu-baseline still drops it)."""
+    import argparse
+    sys.path.insert(0, ROOT)
+    import bench
+    ns = argparse.Namespace
+    assert not bench.want_cpu_baseline(ns(full=False, no_cpu_baseline=False), 1)
+    assert bench.want_cpu_baseline(ns(full=True, no_cpu_baseline=False), 1)
+    assert not bench.want_cpu_baseline(ns(full=True, no_cpu_baseline=True), 1)
+    assert not bench.want_cpu_baseline(ns(full=True, no_cpu_baseline=False), 2)

@@ -99,7 +99,7 @@ def test_configE_1000_step_segments(hip, compute):
     reference's fp32 run, measured and bounded: sample
     <= BF16_SAMPLE, implied eps error <= BF16_EPS."""
     c = TRAJ_E
-    g = golden("golden_trajE.npz")
+    g = {**golden("golden_trajE.npz"), **golden("golden_trajE_19.npz")}   # one file per segment
     m = _unet(c)
     m.set_compute(compute)
     d = create_gaussian_diffusion(steps=1000, noise_schedule="cosine", timestep_respacing="")
@@ -435,7 +435,7 @@ def test_case4_real_shape_10_consecutive_dps_steps(hip, tmp_path, plan):
     (the clamp-mask elements, off the subgrid)."""
     from confild_amd.guided.unet import create_model as guided_model
     c, cs = CASE4_OP, CASE4_STEPS
-    g = golden("golden_case4steps.npz")
+    g = {**golden("golden_case4steps.npz"), **golden("golden_case4steps_final.npz")}   # img_final apart
     op = _case4_operator(tmp_path)
     kw = c["unet"]
     shapes = {k: tuple(v.shape) for k, v in guided_model(**kw).state_dict().items()}

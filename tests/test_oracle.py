@@ -266,7 +266,7 @@ def test_oracle_configE_segment_prefix():
     """First 4 steps of each config-E segment (128^2 U-Net, 1000-step DDPM)."""
     cc = _cfg_cases()
     c = cc.TRAJ_E
-    g = golden("golden_trajE.npz")
+    g = {**golden("golden_trajE.npz"), **golden("golden_trajE_19.npz")}   # one file per segment
     cfg = ou.Config(**c["unet"])
     sd = {k: torch.from_numpy(v) for k, v in cc.unet_weights(ou.param_shapes(cfg), c["seed"]).items()}
     tb = od.Tables(1000, "cosine", "")
@@ -318,7 +318,7 @@ def test_oracle_case4_chain_first_step(tmp_path):
     file-built operator) through the oracle's autograd DPS step."""
     cc = _cfg_cases()
     c, cs = cc.CASE4_OP, cc.CASE4_STEPS
-    g = golden("golden_case4steps.npz")
+    g = {**golden("golden_case4steps.npz"), **golden("golden_case4steps_final.npz")}   # img_final apart
     p = cc.case4_files(str(tmp_path))
     prm = torch.load(p["normalizer"], weights_only=True)
     ssd = torch.load(p["ckpt"], weights_only=True)["model_state_dict"]

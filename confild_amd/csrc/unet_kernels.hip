@@ -1910,6 +1910,13 @@ static int even_splits(int nch, int splits) {
     return (nch + per - 1) / per;
 }
 
+// K1p tile choice: 128x128 tiles from this many of them, else 64x64 from this
+// many, else 32x64 (tools/convbench, variants 40-42 per pointwise shape: 16^2
+// qkv with 144 128x128 tiles 14.8 us against 16.7 on 64x64, 32^2 skip with 128
+// of them 20.4 against 18.0; the 192-tile 64x64 classes 8.9-13.0 us against
+// 9.4-13.8 on 32x64, the 64- and 128-tile ones 9.6 and 8.5 against 7.8 and 7.2)
+constexpr int64_t kK1pMin128 = 144, kK1pMin64 = 192;
+
 ConvPlan plan_conv(const ConvArgs& a, size_t part_cap_floats) {
     // Every choice is made from the per-sample shape at the planned batch (8 unless
     // the model sets another, cfd_unet_set_plan_batch), never from the actual
@@ -1943,6 +1950,20 @@ ConvPlan plan_conv(const ConvArgs& a, size_t part_cap_floats) {
     if (a.ks == 1 && !a.tmode && tiles(p.bm) >= 128) p.splits = 1;
     // memory guard, on the nominal shape too
     while (p.splits > 1 && (size_t)p.splits * mn * a.Cout > part_cap_floats) p.splits /= 2;
+    // K1p (conv_p.hip): the pointwise split-f16 forward convolutions, never split
+    // over K; the tile from the workgroups it gives at the planned batch
+    // Not the one class convbench has slower there: fewer than 32 of the smallest
+    // tiles on a K of 1024 or more (the 8^2 1024->512 skip at planned batch 1, 16
+    // workgroups of 32 K tiles each: 11.6 us against 10.0 split 8 ways on K1s,
+    // reduction included), which keeps the plan above.
+    if (conv_p_applies(a) && !(ceil_div(mn, 32) * ceil_div(a.Cout, 64) < 32 && a.K >= 1024)) {
+        ConvPlan q;
+        const int64_t t128 = ceil_div(mn, 128) * ceil_div(a.Cout, 128), t64 = ceil_div(mn, 64) * ceil_div(a.Cout, 64);
+        q.kx = t128 >= kK1pMin128 ? 40 : t64 >= kK1pMin64 ? 41 : 42;
+        conv_p_tile(q.kx, q.bm, q.bn, q.nw);
+        q.splits = 1;
+        return q;
+    }
     // the large-latent levels (Case4's 192^2 / 384^2) with <= 128 input channels
     // stay on the K1s 128x128 8-wave tiles (tools/convbench at one sample: 384^2
     // 128->128 178 vs K1h 199 us, the 2x upsampling 174 vs 197, 192^2 128->128 63
@@ -2067,19 +2088,25 @@ static bool conv_x_falls_back(const ConvArgs& a) {
     return force_k1s || !(srows < (1 << 24) && a.M < (1 << 24) && srows * std::max(a.C1, a.C2) * 4 < (1ll << 31));
 }
 
+// K1p also needs 32-bit weight offsets and an operand it reads (fp32 sources)
+static bool conv_p_falls_back(const ConvArgs& a) {
+    return !conv_p_applies(a) || (int64_t)a.Cout * a.K * 2 >= (1ll << 31);
+}
+
 bool conv_runs_k1hb(const ConvArgs& a, const ConvPlan& p) { return p.kx == 22 && !conv_x_falls_back(a); }
 
 bool conv_kv_pack_ok(const ConvArgs& a, const ConvPlan& p, int T) {
-    // launch_conv's choices: K1s (a 1x1 never takes K1x), split or bf16 compute
-    // (MODE 2 / 1: bands of whole 32-row blocks), the LDS epilogue on, one split
+    // launch_conv's choices: K1s or K1p (a 1x1 never takes K1x), split or bf16
+    // compute (MODE 2 / 1: bands of whole 32-row blocks; K1p: tiles of them), the
+    // LDS epilogue on (K1p may fall back to K1s), one split
     static const int ldsepi = env_int("CFD_CONV_LDSEPI", 1);
-    return ldsepi && p.kx < 0 && p.splits == 1 && a.wbf && !a.tmode && a.ks == 1 && a.bias &&
+    return ldsepi && (p.kx < 0 || p.kx >= 40) && p.splits == 1 && a.wbf && !a.tmode && a.ks == 1 && a.bias &&
            !a.emb && !a.res && a.Cout % 8 == 0 && a.emb_stride % 4 == 0 && T % 32 == 0 && a.M % T == 0;
 }
 
 int launch_conv(const ConvArgs& a, const ConvPlan& p0, hipStream_t st, bool defer) {
     ConvPlan p = p0;
-    if (p.kx >= 0 && conv_x_falls_back(a)) {
+    if (p.kx >= 0 && (conv_x_falls_back(a) || (p.kx >= 40 && conv_p_falls_back(a)))) {
         p.kx = -1;
         p.bm = p.bn = 128;
         p.nw = 8;
@@ -2116,6 +2143,11 @@ int launch_conv(const ConvArgs& a, const ConvPlan& p0, hipStream_t st, bool defe
                     srows * std::max(a.C1, a.C2) * 4 < (1ll << 31) && (int64_t)a.Cout * a.K * wes < (1ll << 31);
     }
     const ConvArgs& a_ = b;
+    if (p.kx >= 40) {
+        CFD_REQUIRE(p.splits == 1, CFD_ESTATE, "internal: K1p does not split over K");
+        launch_conv_p(a_, p.kx, st);
+        return 1;
+    }
     if (p.kx >= 0) {
         launch_conv_x(a_, p.kx, p.splits, st);
         if (p.splits > 1 && !defer) launch_splitk_reduce(a, p.splits, st);

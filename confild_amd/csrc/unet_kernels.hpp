@@ -148,7 +148,8 @@ struct AttnBwdArgs {
 struct ConvPlan {
     int bm = 128, bn = 128, splits = 1;
     int nw = 4;  // waves per workgroup (8: BM = BN = 128 only)
-    int kx = -1; // >= 0: run the K1x kernel variant (conv_x.hip) instead of conv_gemm_kernel
+    int kx = -1; // >= 0: run the K1x kernel variant (conv_x.hip) instead of conv_gemm_kernel;
+                 // 40-42: the K1p pointwise tiles (conv_p.hip: 128x128, 64x64, 32x64), never split
     int pf = 1;  // K1s: K tiles in flight through registers (set by launch_conv)
 };
 
@@ -206,6 +207,11 @@ __device__ __forceinline__ void xcd_tile(int order, int& bx, int& by, int& bz) {
 // 64x64 wave tiles; variant selects the kernel and tile shape
 int launch_conv_x(const ConvArgs& a, int variant, int splits, hipStream_t st);
 int conv_h_tw(const ConvArgs& a);   // K1h tile width for a shape, 0: not applicable
+// K1p (conv_p.hip): the pointwise split-f16 forward convolutions as a plain GEMM;
+// variant 40 / 41 / 42 selects the 128x128 / 64x64 / 32x64 tile
+bool conv_p_applies(const ConvArgs& a);
+void conv_p_tile(int variant, int& bm, int& bn, int& nw);
+void launch_conv_p(const ConvArgs& a, int variant, hipStream_t st);
 // whether launch_conv runs this plan on K1hb (the bf16 halo kernel, variant 22):
 // the only convolution that reads a bf16 source (ConvArgs::src_bf16)
 int smalln_below();
@@ -226,8 +232,8 @@ void launch_attention_split(const AttnArgs& a, int CH, int heads, int B, int pla
 // the K / V fragment pointers of kvws (launch_attention_split's layout): K at
 // kvws, V at kvws + voff h8v
 int64_t attention_split_voff(int T, int CH, int heads, int B);
-// whether launch_conv runs this qkv plan through a K1s LDS epilogue that can pack
-// the K / V fragments (split compute, no split-K, T % 32 == 0)
+// whether launch_conv runs this qkv plan through a K1s or K1p LDS epilogue that can
+// pack the K / V fragments (split compute, no split-K, T % 32 == 0)
 bool conv_kv_pack_ok(const ConvArgs& a, const ConvPlan& p, int T);
 // backward (unet_vjp.hip)
 int launch_gn_bwd(const GnbArgs& a, int B, hipStream_t st);   // returns the pixel chunks used

@@ -8,6 +8,10 @@
 //   hipcc -O2 --offload-arch=gfx950 -std=c++17 -Iinclude tools/convbench.cpp \
 //         -Lconfild_amd/lib -lconfild_hip -Wl,-rpath,$PWD/confild_amd/lib -o build/convbench
 //   build/convbench [variant ...]          (default: all variants)
+// Variants 40 / 41 / 42 are the K1p pointwise tiles (conv_p.hip: 128x128, 64x64,
+// 32x64) on the 1x1 shapes.  The first line of a shape is the linked library's
+// own plan: link against libconfild_hip_nok1p.so (make VARIANT=nok1p
+// VFLAGS=-DCFD_NO_K1P) for the plans without K1p, reduction launch included.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -37,6 +41,7 @@ int conv_h_tw(const ConvArgs& a);
 struct Shape {
     const char* name;
     int B, Hin, Win, C1, C2, Cout, ks, stride, up;
+    int plan_b = 0;   // the planned batch (0: the default, 8)
 };
 
 static const Shape SHAPES[] = {
@@ -62,6 +67,18 @@ static const Shape SHAPES[] = {
     {"L3 qkv 512->1536", 8, 8, 8, 512, 0, 1536, 1, 1, 0},
     {"L2 qkv 384->1152", 8, 16, 16, 384, 0, 1152, 1, 1, 0},
     {"L1 qkv 256->768", 8, 32, 32, 256, 0, 768, 1, 1, 0},
+    {"L2 proj 384->384", 8, 16, 16, 384, 0, 384, 1, 1, 0},
+    {"L3 proj 512->512", 8, 8, 8, 512, 0, 512, 1, 1, 0},
+    {"B1 L1 qkv 256->768", 1, 32, 32, 256, 0, 768, 1, 1, 0, 1},
+    {"B1 L2 qkv 384->1152", 1, 16, 16, 384, 0, 1152, 1, 1, 0, 1},
+    {"B1 L3 qkv 512->1536", 1, 8, 8, 512, 0, 1536, 1, 1, 0, 1},
+    {"B1 L1 proj 256->256", 1, 32, 32, 256, 0, 256, 1, 1, 0, 1},
+    {"B1 L2 proj 384->384", 1, 16, 16, 384, 0, 384, 1, 1, 0, 1},
+    {"B1 L3 proj 512->512", 1, 8, 8, 512, 0, 512, 1, 1, 0, 1},
+    {"B1 L0 skip1x1 384->128", 1, 64, 64, 256, 128, 128, 1, 1, 0, 1},
+    {"B1 L1 skip1x1 640->256", 1, 32, 32, 384, 256, 256, 1, 1, 0, 1},
+    {"B1 L2 skip1x1 768->384", 1, 16, 16, 384, 384, 384, 1, 1, 0, 1},
+    {"B1 L3 skip1x1 1024->512", 1, 8, 8, 512, 512, 512, 1, 1, 0, 1},
     {"C4 384^2 conv 128->128", 1, 384, 384, 128, 0, 128, 3, 1, 0},
     {"C4 384^2 conv 256->128", 1, 384, 384, 256, 0, 128, 3, 1, 0},
     {"C4 384^2 conv 128->256", 1, 384, 384, 128, 0, 256, 3, 1, 0},
@@ -99,7 +116,7 @@ int main(int argc, char** argv) {
 static int bench_main(int argc, char** argv) {
     std::vector<int> variants;
     for (int i = 1; i < argc; ++i) variants.push_back(atoi(argv[i]));
-    if (variants.empty()) variants = {1, 2, 20};   // the K1x and K1h variants the planner ships (round 3)
+    if (variants.empty()) variants = {1, 2, 20, 40, 41, 42};   // the K1x, K1h and K1p variants the planner ships
     const int splits_x = getenv("CX_SPLITS") ? atoi(getenv("CX_SPLITS")) : 0;   // 0: auto
     hipStream_t st;
     CK(hipStreamCreate(&st));
@@ -173,6 +190,7 @@ static int bench_main(int argc, char** argv) {
         a.Cout = s.Cout;
         a.M = M;
         a.K = K;
+        a.plan_b = s.plan_b;
         const double flops = 2.0 * M * s.Cout * K;
         const int iters = 20;
         hipEvent_t e0, e1;
@@ -194,16 +212,17 @@ static int bench_main(int argc, char** argv) {
         CK(hipMemcpy(r0.data(), out0, r0.size() * 4, hipMemcpyDeviceToHost));
         float rmax = 0.f;
         for (float v : r0) rmax = std::max(rmax, std::fabs(v));
-        printf("%-26s M=%6d N=%4d K=%5d | K1s %3dx%3d/%d split %2d: %8.1f us %6.1f TF\n", s.name, M, s.Cout, K, p.bm,
-               p.bn, p.nw, p.splits, ms0 * 1e3, flops / (ms0 * 1e-3) / 1e12);
+        printf("%-26s M=%6d N=%4d K=%5d | plan kx %2d %3dx%3d/%d split %2d: %8.1f us %6.1f TF\n", s.name, M, s.Cout, K,
+               p.kx, p.bm, p.bn, p.nw, p.splits, ms0 * 1e3, flops / (ms0 * 1e-3) / 1e12);
         for (int v : variants) {
             const int BMv_[] = {128, 128, 256, 128, 64, 64, 64, 128, 64, 128}, BNv_[] = {128, 128, 128, 64, 128, 64, 64, 64, 128, 128};
             const int vb = v >= 10 ? 0 : v;
             if (v == 30 && !splits_x) continue;
             const int BMv = v == 21 ? 128 : v >= 20 ? 256 : BMv_[vb], BNv = BNv_[vb];
             if ((v == 20 || v == 21) && !cfd::conv_h_tw(a)) continue;
+            if (v >= 40 && !cfd::conv_p_applies(a)) continue;
             const int64_t tiles = ((M + BMv - 1) / BMv) * ((s.Cout + BNv - 1) / BNv);
-            int splits = splits_x;
+            int splits = v >= 40 ? 1 : splits_x;
             if (!splits) {
                 splits = 1;
                 if (v == 20 || v == 21)
@@ -222,6 +241,10 @@ static int bench_main(int argc, char** argv) {
             auto run = [&]() {
                 if (v == 30) {
                     cfd::launch_conv(b, p30, st, false);
+                    return;
+                }
+                if (v >= 40) {
+                    cfd::launch_conv_p(b, v, st);
                     return;
                 }
                 cfd::launch_conv_x(b, v, splits, st);

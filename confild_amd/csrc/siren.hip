@@ -289,15 +289,15 @@ __global__ __launch_bounds__(256) void gemm_splitk_reduce_kernel(const float* __
 
 // split-K count of a latent-side GEMM: a function of K only (never of M, the
 // latent rows), so a row's result does not depend on how many rows share the call
-static int gemm_splits(int K) {
+int gemm_splits(int K) {
     int s = 1;
     while (s < 16 && K / (2 * s) >= 256 && K % (32 * s) == 0) s *= 2;
     return s;
 }
 
 // part: scratch of gemm_splits(K) * M * ldc floats (used when that is > 1)
-static void launch_gemm_f32(bool bt, const float* A, int lda, const float* B, int ldb, const float* bias, float* C,
-                            int ldc, int M, int N, int K, hipStream_t st, float* part = nullptr) {
+void launch_gemm_f32(bool bt, const float* A, int lda, const float* B, int ldb, const float* bias, float* C, int ldc,
+                     int M, int N, int K, hipStream_t st, float* part) {
     CFD_REQUIRE(K % 16 == 0 && lda % 4 == 0 && ldb % 4 == 0 && (bt || N % 4 == 0), CFD_ESHAPE,
                 "gemm_f32: K % 16, leading dims % 4");
     const int splits = part ? gemm_splits(K) : 1;
@@ -1040,34 +1040,9 @@ __global__ __launch_bounds__(256) void siren_latent_grad(const float* __restrict
 // ---------------------------------------------------------------------------
 // handle
 // ---------------------------------------------------------------------------
-struct SirenParam {
-    std::string key;
-    std::vector<int64_t> shape;
-    bool set = false;
-};
+// (SirenParam, struct cfd_siren: siren.hpp)
 
 }  // namespace cfd
-
-struct cfd_siren {
-    cfd_siren_cfg cfg;
-    int device = 0;
-    int NB = 0;
-    std::vector<cfd::SirenParam> params;
-    float* w0 = nullptr;    // (H, d)
-    float* fbias = nullptr; // (nh+1, H)
-    float* V = nullptr;     // (nh+1, H, L)
-    float* wimg = nullptr;  // nh * NB * NB*256
-    float* wout = nullptr;  // (c, H)
-    float* bout = nullptr;  // (c)
-    float* wimg_t = nullptr; // transposed weight image, layers nh..1 (latent-gradient path)
-    float* wimg16 = nullptr; // split-f16 image (hi, lo) of the scaled hidden weights, same bytes as wimg
-    float* wimg16t = nullptr; // the same image of the transposes, layers nh..1 (K9t backward)
-    float* wscale = nullptr; // (nh) power-of-two scale of each hidden layer in wimg16
-    float* wimg32 = nullptr; // the same split in the 32x32x16 chain's k order (siren_split32)
-    float* wimg32r = nullptr; // siren_split32 image of W (w0 / 2pi) s'_i: accumulators in revolutions
-    float* wrev = nullptr;    // (2 nh): (w0 / 2pi) s'_i, then 1 / s'_i
-    int compute = CFD_SIREN_SPLIT_F16;
-};
 
 namespace {
 
@@ -1353,7 +1328,8 @@ extern "C" int cfd_siren_workspace_bytes(const cfd_siren* h, int b, size_t* byte
 
 // FiLM vectors F_i = b_i + V_i z of b latent rows, (b, nl, H): one fp32 MFMA GEMM
 // (the per-row VALU kernel for latent widths the GEMM tiling does not take)
-static void film_vectors(const cfd_siren* h, const float* latents, int b, float* film, hipStream_t st) {
+namespace cfd {
+void film_vectors(const cfd_siren* h, const float* latents, int b, float* film, hipStream_t st) {
     const int nl = h->cfg.num_hidden_layers + 1, H = h->cfg.hidden_features, L = h->cfg.in_latent_features;
     if (L % 16 == 0) {
         cfd::launch_gemm_f32(true, latents, L, h->V, L, h->fbias, film, nl * H, b, nl * H, L, st);
@@ -1362,6 +1338,8 @@ static void film_vectors(const cfd_siren* h, const float* latents, int b, float*
     hipLaunchKernelGGL(cfd::siren_film, dim3(nl, b), dim3(128), 0, st, h->V, h->fbias, latents, film, H, L, nl);
     cfd::check_launch("siren_film");
 }
+}  // namespace cfd
+using cfd::film_vectors;
 
 extern "C" int cfd_siren_forward(cfd_siren* h, const float* coords, int64_t N, const float* latents, int b,
                                  const float* xmax, const float* xmin, const float* ymax, const float* ymin,

@@ -1,8 +1,10 @@
 // Shared pieces of the fused SIREN decoders (siren.hip: exact fp32 MFMA chain;
 // siren_split.hip: fp32-accurate split-f16 MFMA chain).
 #pragma once
+#include <string>
 #include <type_traits>
 #include <utility>
+#include <vector>
 
 #include "common.hpp"
 
@@ -113,5 +115,45 @@ void launch_siren_split32(int H, SirenArgs a, int b, hipStream_t st);
 // split-f16 K-split tape kernels (K9t, siren_split.hip): null when NB has no form
 bool tape_split_supported(int NB);
 void launch_tape_split(int NB, const SirenTapeArgs& a, bool bwd, hipStream_t st);
+void launch_tape_split_sum(int NB, const SirenTapeArgs& a, int rows, hipStream_t st);
+
+struct SirenParam {
+    std::string key;
+    std::vector<int64_t> shape;
+    bool set = false;
+};
+
+}  // namespace cfd
+
+struct cfd_siren {
+    cfd_siren_cfg cfg;
+    int device = 0;
+    int NB = 0;
+    std::vector<cfd::SirenParam> params;
+    float* w0 = nullptr;    // (H, d)
+    float* fbias = nullptr; // (nh+1, H)
+    float* V = nullptr;     // (nh+1, H, L)
+    float* wimg = nullptr;  // nh * NB * NB*256
+    float* wout = nullptr;  // (c, H)
+    float* bout = nullptr;  // (c)
+    float* wimg_t = nullptr; // transposed weight image, layers nh..1 (latent-gradient path)
+    float* wimg16 = nullptr; // split-f16 image (hi, lo) of the scaled hidden weights, same bytes as wimg
+    float* wimg16t = nullptr; // the same image of the transposes, layers nh..1 (K9t backward)
+    float* wscale = nullptr; // (nh) power-of-two scale of each hidden layer in wimg16
+    float* wimg32 = nullptr; // the same split in the 32x32x16 chain's k order (siren_split32)
+    float* wimg32r = nullptr; // siren_split32 image of W (w0 / 2pi) s'_i: accumulators in revolutions
+    float* wrev = nullptr;    // (2 nh): (w0 / 2pi) s'_i, then 1 / s'_i
+    int compute = CFD_SIREN_SPLIT_F16;
+    int dense_bwd = CFD_DENSE_BWD_SUM;          // dense DPS adjoint forms (dps_dense.hip,
+    int dense_compute = CFD_DENSE_COMPUTE_AUTO;  // cfd_siren_dense_set_form)
+};
+
+namespace cfd {
+
+// latent-side pieces of siren.hip shared with the dense DPS adjoint (dps_dense.hip)
+int gemm_splits(int K);
+void launch_gemm_f32(bool bt, const float* A, int lda, const float* B, int ldb, const float* bias, float* C, int ldc,
+                     int M, int N, int K, hipStream_t st, float* part = nullptr);
+void film_vectors(const cfd_siren* h, const float* latents, int b, float* film, hipStream_t st);
 
 }  // namespace cfd

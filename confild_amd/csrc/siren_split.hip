@@ -1028,7 +1028,14 @@ __global__ __launch_bounds__(64 * KS) void siren_tape_fwd_split(SirenTapeArgs p)
     }
 }
 
-template <int NB, int KS, int RING>
+// SUM (the dense DPS adjoint, dps_dense.hip): the 16-pair tiles are aligned to rows --
+// grid (16-point tile, row), Ns points per row -- and instead of every delta the tile's
+// sum over its 16 points is stored, one (nh+1) H partial per tile at p.delta: each
+// delta store becomes a rotate-and-add over the lane row (DPP row_ror 8, 4, 2, 1) and
+// one store by the row's first lane -- the same count of memory instructions, so the
+// vmcnt accounting above holds.  Points past the row's end get a zero output gradient:
+// all their deltas are exact zeros.
+template <int NB, int KS, int RING, bool SUM = false>
 __global__ __launch_bounds__(64 * KS) void siren_tape_bwd_split(SirenTapeArgs p) {
     constexpr int H = NB * 16, BLK = NB * 256, QW = NB / KS, QC = QW / 2;
     static_assert(QW % 2 == 0 && (RING == 2 || RING == 3), "K9t: an even block count per wave");
@@ -1038,12 +1045,42 @@ __global__ __launch_bounds__(64 * KS) void siren_tape_bwd_split(SirenTapeArgs p)
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int g = lane >> 4, j16 = lane & 15;
-    const int64_t n = (int64_t)blockIdx.x * 16 + j16;
-    const int64_t nc = n < p.P ? n : p.P - 1;
-    const int sensor = (int)(nc % p.Ns);
     const int nh = p.nh, nl = nh + 1;
+    int64_t nc;
+    int sensor;
+    bool live = true;
+    float* dt;
+    if constexpr (SUM) {
+        const int pt = (int)blockIdx.x * 16 + j16;
+        live = pt < p.Ns;
+        sensor = live ? pt : p.Ns - 1;
+        nc = (int64_t)blockIdx.y * p.Ns + sensor;
+        dt = p.delta + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * nl * H;
+    } else {
+        const int64_t n = (int64_t)blockIdx.x * 16 + j16;
+        nc = n < p.P ? n : p.P - 1;
+        sensor = (int)(nc % p.Ns);
+        dt = p.delta + nc * nl * H;
+    }
+    CFD_DASSERT(nc >= 0 && nc < p.P);
     const float* ut = p.u + nc * nl * H;
-    float* dt = p.delta + nc * nl * H;
+    // a delta's tape store, or the store of its sum over the tile's 16 points
+    auto put = [&](float* dst, f4 dd) __attribute__((always_inline)) {
+        if constexpr (SUM) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                float v = dd[r];
+                v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x128, 0xf, 0xf, false));
+                v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x124, 0xf, 0xf, false));
+                v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x122, 0xf, 0xf, false));
+                v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x121, 0xf, 0xf, false));
+                dd[r] = v;
+            }
+            if (j16 == 0) *(f4*)dst = dd;
+        } else {
+            *(f4*)dst = dd;
+        }
+    };
     const float w0f = p.w0f;
     const int q0 = wave * QW;
     const int nblocks = nh * NB;
@@ -1055,7 +1092,7 @@ __global__ __launch_bounds__(64 * KS) void siren_tape_bwd_split(SirenTapeArgs p)
 #pragma unroll
     for (int oc = 0; oc < 4; ++oc) {
         if (oc < p.c) {
-            float v = p.gout[nc * p.c + oc];
+            float v = live ? p.gout[nc * p.c + oc] : 0.f;
             if (p.ymax) {
                 const int64_t yi = (int64_t)sensor * p.ystride + oc;
                 v = v * ((p.ymax[yi] - p.ymin[yi]) / 2.0f);
@@ -1079,7 +1116,7 @@ __global__ __launch_bounds__(64 * KS) void siren_tape_bwd_split(SirenTapeArgs p)
             dd[r] = gx * (w0f * cos_cw(w0f * uu[r]));
             X[qq][r] = dd[r];
         }
-        *(f4*)(dt + nh * H + 16 * q + 4 * g) = dd;
+        put(dt + nh * H + 16 * q + 4 * g, dd);
     });
     // this wave's slice of a pair's deltas, scaled by 2^-e into [0.5, 1) and split;
     // returns e (0 for an all-zero slice)
@@ -1155,7 +1192,7 @@ __global__ __launch_bounds__(64 * KS) void siren_tape_bwd_split(SirenTapeArgs p)
             });
             if constexpr (j > 0) {
                 if (own) {
-                    *(f4*)(dt + li * H + 16 * jp + 4 * g) = dd;
+                    put(dt + li * H + 16 * jp + 4 * g, dd);
 #pragma unroll
                     for (int r = 0; r < 4; ++r) Xn[jp % QW][r] = dd[r];
                 }
@@ -1187,7 +1224,7 @@ __global__ __launch_bounds__(64 * KS) void siren_tape_bwd_split(SirenTapeArgs p)
                 dd[r] = acc[r] * (w0f * cos_cw(w0f * uur[qq][r]));
                 Xn[qq][r] = dd[r];
             }
-            *(f4*)(dt + li * H + 16 * (NB - 1) + 4 * g) = dd;
+            put(dt + li * H + 16 * (NB - 1) + 4 * g, dd);
         }
         static_for<QW>([&](auto qc) {
             constexpr int qq = decltype(qc)::value;
@@ -1217,6 +1254,30 @@ void launch_tape_split_nb(const SirenTapeArgs& a, bool bwd, hipStream_t st) {
     check_launch(bwd ? "siren_tape_bwd_split" : "siren_tape_fwd_split");
 }
 }  // namespace
+
+namespace {
+template <int NB, int KS>
+void launch_tape_split_sum_nb(const SirenTapeArgs& a, int rows, hipStream_t st) {
+    constexpr int RING = 3;
+    const size_t lds = sizeof(float) * ((size_t)RING * NB * 256 + 2 * KS * 256);
+    const void* fn = (const void*)siren_tape_bwd_split<NB, KS, RING, true>;
+    CFD_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const dim3 grid((unsigned)ceil_div(a.Ns, 16), (unsigned)rows);
+    hipLaunchKernelGGL((siren_tape_bwd_split<NB, KS, RING, true>), grid, dim3(64 * KS), lds, st, a);
+    check_launch("siren_tape_bwd_split(sum)");
+}
+}  // namespace
+
+// sum-mode K9t backward: a.delta receives (rows, ceil(Ns / 16), (nh+1) H) tile sums
+void launch_tape_split_sum(int NB, const SirenTapeArgs& a, int rows, hipStream_t st) {
+    CFD_REQUIRE(a.wimg16t && a.wscale && a.P == (int64_t)rows * a.Ns, CFD_ESTATE, "internal: split tape sum arguments");
+    switch (NB) {
+        case 8: return launch_tape_split_sum_nb<8, 4>(a, rows, st);
+        case 16: return launch_tape_split_sum_nb<16, 4>(a, rows, st);
+        case 24: return launch_tape_split_sum_nb<24, 4>(a, rows, st);
+        default: throw Error{CFD_EARG, "split-f16 tape needs hidden_features in {128, 256, 384}"};
+    }
+}
 
 // K9t takes 4 waves per tile where 4 divides the block count into even shares
 bool tape_split_supported(int NB) { return NB == 8 || NB == 16 || NB == 24; }

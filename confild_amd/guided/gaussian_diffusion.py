@@ -5,7 +5,7 @@ One reverse step of the 'ps' (DPS) loop, reference (gaussian_diffusion.py:
 169-206, 362-372; condition_methods.py:31-47,81-90):
 
     out = p_sample(x)                      # eps = U(x, t); x0 = clamp(c1 x - c2 eps); sample
-    norm = ||y - A(x0)||                   # A = Case4Operator.forward
+    norm = ||y - A(x0)||                   # A = the operator's forward (mask * fields with a mask)
     x = out.sample - scale * d norm / d x  # torch autograd through A, clamp, U
 
 Here, with the same arithmetic per link:
@@ -18,6 +18,12 @@ Here, with the same arithmetic per link:
     d_eps, g_direct = cfd_dps_latent_grad(g_z)            (unnorm, clamp', c1 / c2 links)
     g_unet  = cfd_unet_input_vjp(d_eps)
     x       = cfd_dps_update(sample, g_direct, g_unet, scale)
+
+Case4Operator without a mask runs exactly that.  Every other operator (case2,
+case3, case3_gappy), and any operator with ``partial(cond_method.conditioning,
+mask=mask)``, replaces the three SIREN / residual lines by one call,
+
+    g_z, norm = cfd_siren_dense_grad(unnorm(x0), y, mask) (bounded workspace)
 
 Batches: the reference loop only runs one sample per call (its ``if t != 0``
 needs a one-element t; the notebook loops over samples).  Here a batch of B
@@ -41,6 +47,7 @@ from ..gaussian_diffusion import (LossType, ModelMeanType, ModelVarType, STEP_DD
                                   fresh_seed, get_named_beta_schedule)
 from ..respace import SpacedDiffusion, space_timesteps
 from .condition_methods import Identity, PosteriorSampling
+from .measurements import Case4Operator
 
 __SAMPLER__ = {}
 
@@ -84,15 +91,48 @@ def create_sampler(sampler, steps, noise_schedule, model_mean_type, model_var_ty
                loss_type=LossType.MSE, rescale_timesteps=False, clip_denoised=clip_denoised)
 
 
+_COND_KEYWORDS = ("mask",)
+
+
 def _method_of(measurement_cond_fn):
+    """(method, keywords) behind ``partial(cond_method.conditioning, **keywords)``: the
+    keywords of the whole partial chain (an outer partial's win, as when called).
+    ``mask`` is the one the operators take (measurements.py:92); any other raises."""
     fn = measurement_cond_fn
+    kw = {}
     while isinstance(fn, functools.partial):
+        for k, v in fn.keywords.items():
+            kw.setdefault(k, v)
         fn = fn.func
     owner = getattr(fn, "__self__", None)
-    if isinstance(owner, (PosteriorSampling, Identity)):
-        return owner
-    raise NotImplementedError("measurement_cond_fn must be partial(cond_method.conditioning) of a 'ps' or "
-                              "'vanilla' method from confild_amd.guided.condition_methods")
+    if not isinstance(owner, (PosteriorSampling, Identity)):
+        raise NotImplementedError("measurement_cond_fn must be partial(cond_method.conditioning) of a 'ps' or "
+                                  "'vanilla' method from confild_amd.guided.condition_methods")
+    for k in kw:
+        if k not in _COND_KEYWORDS:
+            raise NotImplementedError(f"keyword {k!r} of measurement_cond_fn is not supported on the HIP path "
+                                      f"(supported: {', '.join(_COND_KEYWORDS)})")
+    return owner, kw
+
+
+def _mask_tables(mask, op, B, T, N, c, dev):
+    """The mask keyword (and the operator's own mask) as 1, T or B*T tables of (N, c)
+    on the device, or None.  Masks broadcastable to (T, N, c) or (B*T, N, c)."""
+    own = op.default_mask() if hasattr(op, "default_mask") else None
+    if mask is None and own is None:
+        return None
+    if mask is None:
+        return own.to(device=dev, dtype=torch.float32).reshape(1, N, c).contiguous()
+    m = torch.as_tensor(mask).to(device=dev, dtype=torch.float32)
+    if own is not None:
+        m = m * own.to(device=dev, dtype=torch.float32)
+    if m.dim() > 3:
+        raise ValueError(f"mask of shape {tuple(m.shape)} has more than 3 dimensions")
+    lead = m.shape[0] if m.dim() == 3 else 1
+    if lead not in (1, T, B * T):
+        raise ValueError(f"mask of shape {tuple(m.shape)} broadcasts to neither ({T}, {N}, {c}) nor "
+                         f"({B * T}, {N}, {c})")
+    return torch.broadcast_to(m, (lead, N, c)).contiguous()
 
 
 class _GuidedSampler(SpacedDiffusion):
@@ -102,6 +142,7 @@ class _GuidedSampler(SpacedDiffusion):
         super().__init__(use_timesteps, **kwargs)
         self.clip_denoised = clip_denoised
         self.distances = None   # (steps, B) residual norms of the last p_sample_loop (GPU)
+        self.dense_budget = None  # workspace bytes the dense adjoint may plan for (None: the library default)
 
     def p_sample_loop(self, model, x_start, measurement, measurement_cond_fn, record=False, save_root=None, *,
                       step_noise=None, seed=None, sample_offset=0, progress=False):
@@ -110,9 +151,10 @@ class _GuidedSampler(SpacedDiffusion):
         ``self.distances`` (steps, B) on the GPU."""
         if record:
             raise NotImplementedError("record=True (progress images) is not part of the HIP path")
-        method = _method_of(measurement_cond_fn)
+        method, kw = _method_of(measurement_cond_fn)
         if x_start.device.type != "cuda":
             raise _lib.CfdError("the DPS sampler runs on the GPU only (no CPU fallback)")
+        mask = self._device_mask(method, kw, x_start)
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
         x = x_start.detach().to(torch.float32).contiguous().clone()
@@ -123,7 +165,8 @@ class _GuidedSampler(SpacedDiffusion):
             indices = tqdm(indices)
         for k, i in enumerate(indices):
             nz = None if step_noise is None else step_noise[k]
-            x = self._guided_step(model, x, i, measurement, method, nz, seed, k, sample_offset, self.distances[k])[0]
+            x = self._guided_step(model, x, i, measurement, method, nz, seed, k, sample_offset, self.distances[k],
+                                  mask)[0]
         check_model_range(model, x.device)
         return x
 
@@ -133,16 +176,27 @@ class _GuidedSampler(SpacedDiffusion):
         gaussian_diffusion.py:188-199).  Returns dict(sample, pred_xstart, x_t, distance):
         the conditioned image, x0_hat, the unconditioned DDPM/DDIM sample, the norms.
         Without ``noise`` and ``seed`` the step draws a fresh Philox key (fresh_seed)."""
-        method = _method_of(measurement_cond_fn)
+        method, kw = _method_of(measurement_cond_fn)
         seed = fresh_seed(noise, seed)
         x = x.detach().to(torch.float32).contiguous().clone()
         dist = torch.zeros(x.shape[0], dtype=torch.float32, device=x.device)
         img, x0, sample = self._guided_step(model, x, index, measurement, method, noise, seed, counter,
-                                            sample_offset, dist)
+                                            sample_offset, dist, self._device_mask(method, kw, x))
         return {"sample": img, "pred_xstart": x0, "x_t": sample, "distance": dist}
 
-    def _guided_step(self, model, x, i, measurement, method, noise, seed, counter, sample_offset, dist_out):
-        """x (B, 1, T, L) contiguous fp32 on the GPU; updated in place for 'ps'."""
+    @staticmethod
+    def _device_mask(method, kw, x):
+        """The mask tables of a 'ps' run on x's device (once per loop, not per step)."""
+        if not isinstance(method, PosteriorSampling):
+            return None
+        op = method.operator
+        return _mask_tables(kw.get("mask"), op, x.shape[0], x.shape[2], op.coords.shape[0], op.model.out_features,
+                            x.device)
+
+    def _guided_step(self, model, x, i, measurement, method, noise, seed, counter, sample_offset, dist_out,
+                     mask=None):
+        """x (B, 1, T, L) contiguous fp32 on the GPU; updated in place for 'ps'.
+        mask: None or the (1 | T | B*T, N, c) device tables of _mask_tables."""
         dev = x.device
         if dev.type != "cuda":
             raise _lib.CfdError("the DPS sampler runs on the GPU only (no CPU fallback)")
@@ -172,15 +226,20 @@ class _GuidedSampler(SpacedDiffusion):
         vmax, vmin = op._bounds()
         if n % vmax.numel():
             raise ValueError("latent max/min do not tile the latent")
-        A = op.forward_tape(x0)                                      # (B*T, Ns, c)
-        per = A.numel() // B
-        if y.numel() not in (per, A.numel()):
-            raise ValueError(f"measurement of {y.numel()} values matches neither one sample ({per}) "
-                             f"nor the batch ({A.numel()})")
-        gA = torch.empty_like(A)
-        _lib.check(lib.cfd_dps_residual(_lib.ptr(y), 0 if y.numel() == per else per, _lib.ptr(A), _lib.ptr(gA),
-                                        _lib.ptr(dist_out), per, B, st), "cfd_dps_residual")
-        gz = op.vjp(gA)                                              # (B*T, L)
+        if isinstance(op, Case4Operator) and mask is None:
+            A = op.forward_tape(x0)                                      # (B*T, Ns, c)
+            per = A.numel() // B
+            if y.numel() not in (per, A.numel()):
+                raise ValueError(f"measurement of {y.numel()} values matches neither one sample ({per}) "
+                                 f"nor the batch ({A.numel()})")
+            gA = torch.empty_like(A)
+            _lib.check(lib.cfd_dps_residual(_lib.ptr(y), 0 if y.numel() == per else per, _lib.ptr(A), _lib.ptr(gA),
+                                            _lib.ptr(dist_out), per, B, st), "cfd_dps_residual")
+            gz = op.vjp(gA)                                              # (B*T, L)
+        else:
+            # a dense or masked measurement: norm and latent gradient in bounded memory
+            gz, norms = op.dense_grad(x0, y, mask, self.dense_budget)
+            dist_out.copy_(norms)
         d_eps = torch.empty_like(x)
         g_dir = torch.empty_like(x)
         _lib.check(lib.cfd_dps_latent_grad(sched.handle, clip, _lib.ptr(x), _lib.ptr(eps), _lib.ptr(t), _lib.ptr(gz),

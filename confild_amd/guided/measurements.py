@@ -1,8 +1,10 @@
 """Measurement operators and noises (C/src/guided_diffusion/measurements.py).
 
-Only the Case4 operator is on the CoNFiLD path.  Its
-forward is the fused HIP SIREN decode at the sensor coordinates; the DPS
-sampler additionally uses ``forward_tape`` / ``vjp`` (the latent gradient).
+The CoNFiLD operators case2, case3, case3_gappy and case4 (SURVEY.md section 8
+a17).  Their forward is the fused HIP SIREN decode at the measured coordinates.
+The DPS sampler additionally uses ``forward_tape`` / ``vjp`` (Case4's 10-sensor
+latent gradient, the whole tape in memory) or ``dense_grad`` (a dense or masked
+measurement: residual norm and latent gradient in bounded memory).
 """
 from __future__ import annotations
 
@@ -56,36 +58,12 @@ def _siren_dims(sd):
     return first.shape[1], sd["net2.0.weight"].shape[1], last.shape[0], len(n1) - 2, first.shape[0]
 
 
-@register_operator(name="case4")
-class Case4Operator(NonLinearOperator):
-    """measurements.py:184-226.  The reference hard-codes SIRENAutodecoder_film(3,
-    384, 3, 15, 384); here the dimensions are read from the checkpoint (identical
-    for the reference's checkpoint, and usable for others)."""
+class _SirenFieldOperator(NonLinearOperator):
+    """What the SIREN-decoding operators share: latents (s, 1, t, l) in [-1, 1] are
+    un-normalised with max_val / min_val, flattened to rows and decoded at
+    ``coords`` through the '-11' x / y normalisers."""
 
-    def __init__(self, device, coords_path, batch_size, max_val_path, min_val_path, normalizer_params_path,
-                 ckpt_path) -> None:
-        self.device = device
-        coords = np.load(coords_path)
-        self.coords = torch.tensor(coords, dtype=torch.float32, device=device)
-        params = torch.load(normalizer_params_path, weights_only=True, map_location="cpu")
-        x_uub, x_llb = params["x_normalizer_params"]
-        y_uub, _ = params["y_normalizer0u_params"]
-        _, y_llb = params["y_normalizer0l_params"]
-        cin_size, cout_size = 3, 3
-        self.x_normalizer = Normalizer_ts(method="-11", dim=0, params=(x_uub, x_llb))
-        self.y_normalizer = Normalizer_ts(method="-11", dim=0, params=(y_uub[:cout_size], y_llb[:cout_size]))
-        ckpt = torch.load(ckpt_path, weights_only=True, map_location="cpu")
-        sd = ckpt["model_state_dict"]
-        d, L, c, nh, H = _siren_dims(sd)
-        if d != cin_size or c != cout_size:
-            raise ValueError(f"Case4 SIREN must map 3 coordinates to 3 outputs, checkpoint has {d} -> {c}")
-        self.model = SIRENAutodecoder_film(d, L, c, nh, H)
-        self.model.load_state_dict(sd)
-        self.model.eval()
-        self.model.to(device)
-        self.max_val = torch.from_numpy(np.load(max_val_path)).to(device)
-        self.min_val = torch.from_numpy(np.load(min_val_path)).to(device)
-        self.batch_size = batch_size
+    _name = "SIREN"
 
     @classmethod
     def from_parts(cls, device, coords, x_normalizer, y_normalizer, model, max_val, min_val, batch_size=384):
@@ -99,6 +77,18 @@ class Case4Operator(NonLinearOperator):
         op.batch_size = batch_size
         return op
 
+    def _load_model(self, ckpt_path, cin_size, cout_size, device):
+        ckpt = torch.load(ckpt_path, weights_only=True, map_location="cpu")
+        sd = ckpt["model_state_dict"]
+        d, L, c, nh, H = _siren_dims(sd)
+        if d != cin_size or c != cout_size:
+            raise ValueError(f"{self._name} SIREN must map {cin_size} coordinates to {cout_size} outputs, "
+                             f"checkpoint has {d} -> {c}")
+        self.model = SIRENAutodecoder_film(d, L, c, nh, H)
+        self.model.load_state_dict(sd)
+        self.model.eval()
+        self.model.to(device)
+
     def _unnorm(self, norm_data):
         return ((norm_data[:, 0, ...] + 1) * (self.max_val - self.min_val) / 2 + self.min_val)[:, None, ...]
 
@@ -110,18 +100,137 @@ class Case4Operator(NonLinearOperator):
     def _rows(self, data):
         """_unnorm + rearrange "s c t l -> (s c t) l" on the GPU (cfd_latent_denorm)."""
         if data.dim() != 4 or data.shape[1] != 1:
-            raise ValueError(f"Case4 latents must be (s, 1, t, l), got {tuple(data.shape)}")
+            raise ValueError(f"{self._name} latents must be (s, 1, t, l), got {tuple(data.shape)}")
         vmax, vmin = self._bounds()
         z = latent_denorm(data.detach().to(torch.float32).contiguous(), vmax, vmin)
         return z.reshape(-1, data.shape[-1])
 
-    def forward(self, data, **kwargs):
-        """(s, 1, t, l) latents in [-1, 1] -> (s*t, Ns, 3) measurements (one fused launch;
-        pass_through_model_batch's row chunking does not change values)."""
+    def _fields(self, data):
         with torch.no_grad():
             return self.model.decode(self.coords, self._rows(data)[:, None], self.x_normalizer, self.y_normalizer)
 
+    def default_mask(self):
+        """The mask the operator itself applies ((Ns, c) table), or None."""
+        return None
+
+    def forward(self, data, **kwargs):
+        """(s, 1, t, l) latents in [-1, 1] -> (s*t, Ns, c) measurements (one fused launch;
+        pass_through_model_batch's row chunking does not change values)."""
+        return self._fields(data)
+
     # -- adjoint used by the DPS sampler ----------------------------------------
+    def dense_grad(self, data, measurement, mask=None, budget=None):
+        """(g_z (s*t, l), norms (s)): the masked residual norm ||y - mask * forward(data)||
+        per sample and its gradient w.r.t. the un-normalised latent rows, in bounded
+        memory (SIRENAutodecoder_film.dense_grad)."""
+        return self.model.dense_grad(self.coords, self._rows(data), data.shape[2], measurement, mask,
+                                     self.x_normalizer, self.y_normalizer, budget)
+
+
+@register_operator(name="case2")
+class Case2Operator(_SirenFieldOperator):
+    """measurements.py:58-97: a full 2-D field (2 coordinates -> 4 outputs) times a
+    ``mask`` keyword.  The reference hard-codes SIRENAutodecoder_film(2, 256, 4, 10,
+    256); here the dimensions are read from the checkpoint.  The normalisers are the
+    reference's constants."""
+
+    _name = "Case2"
+
+    def __init__(self, device, ckpt_path, max_val, min_val, coords, batch_size):
+        self.device = device
+        self.coords = torch.tensor(coords, dtype=torch.float32, device=device)
+        self.x_normalizer = Normalizer_ts(method="-11", dim=0,
+                                          params=[torch.tensor([1., 1.], device=device),
+                                                  torch.tensor([0., 0.], device=device)])
+        self.y_normalizer = Normalizer_ts(method="-11", dim=0,
+                                          params=[torch.tensor([[0.9617, 0.2666, 0.2869, 0.0290]], device=device),
+                                                  torch.tensor([[-0.0051, -0.2073, -0.2619, -0.0419]], device=device)])
+        self._load_model(ckpt_path, 2, 4, device)
+        self.max_val = torch.from_numpy(max_val).to(device)
+        self.min_val = torch.from_numpy(min_val).to(device)
+        self.batch_size = batch_size
+
+    def forward(self, data, mask=None, **kwargs):
+        """mask * fields; without a mask the fields themselves (the reference fails on
+        ``None * fields``)."""
+        out = self._fields(data)
+        return out if mask is None else torch.as_tensor(mask).to(device=out.device, dtype=out.dtype) * out
+
+
+@register_operator(name="case3")
+class Case3Operator(_SirenFieldOperator):
+    """measurements.py:99-137: sensors on the periodic hill (2 -> 2)."""
+
+    _name = "Case3"
+
+    def __init__(self, device, coords, batch_size, max_val, min_val, normalizer_params_path, ckpt_path) -> None:
+        self.device = device
+        self.coords = torch.tensor(coords, dtype=torch.float32, device=device)
+        params = torch.load(normalizer_params_path, weights_only=True, map_location="cpu")
+        x_ub, x_lb = params["x_normalizer_params"]
+        y_ub, y_lb = params["y_normalizer_params"]
+        cin_size, cout_size = 2, 2
+        self.x_normalizer = Normalizer_ts(method="-11", dim=0, params=(x_ub, x_lb))
+        self.y_normalizer = Normalizer_ts(method="-11", dim=0, params=(y_ub[:cout_size], y_lb[:cout_size]))
+        self._load_model(ckpt_path, cin_size, cout_size, device)
+        self.max_val = torch.from_numpy(max_val).to(device)
+        self.min_val = torch.from_numpy(min_val).to(device)
+        self.batch_size = batch_size
+
+    def forward(self, data, mask=None, **kwargs):
+        out = self._fields(data)
+        return out if mask is None else torch.as_tensor(mask).to(device=out.device, dtype=out.dtype) * out
+
+
+@register_operator(name="case3_gappy")
+class Case3Operator_gappy(Case3Operator):
+    """measurements.py:139-181: Case3 with one velocity component blanked per sensor
+    group -- channel 1 for the first 10 sensors, channel 0 for the rest (:179-180),
+    kept here as a (Ns, c) 0/1 table.  The reference's forward hands its arguments
+    to pass_through_model_batch in the wrong order (batch_size where the x normaliser
+    belongs) and cannot run; this builds its evident intent: Case3's fields with
+    those entries set to zero."""
+
+    _name = "Case3 (gappy)"
+    GAP = 10   # sensors whose channel 1 is blanked
+
+    def default_mask(self):
+        m = torch.ones(self.coords.shape[0], self.model.out_features, dtype=torch.float32, device=self.coords.device)
+        m[:self.GAP, 1] = 0.
+        m[self.GAP:, 0] = 0.
+        return m
+
+    def forward(self, data, mask=None, **kwargs):
+        out = self._fields(data) * self.default_mask()
+        return out if mask is None else torch.as_tensor(mask).to(device=out.device, dtype=out.dtype) * out
+
+
+@register_operator(name="case4")
+class Case4Operator(_SirenFieldOperator):
+    """measurements.py:184-226.  The reference hard-codes SIRENAutodecoder_film(3,
+    384, 3, 15, 384); here the dimensions are read from the checkpoint (identical
+    for the reference's checkpoint, and usable for others)."""
+
+    _name = "Case4"
+
+    def __init__(self, device, coords_path, batch_size, max_val_path, min_val_path, normalizer_params_path,
+                 ckpt_path) -> None:
+        self.device = device
+        coords = np.load(coords_path)
+        self.coords = torch.tensor(coords, dtype=torch.float32, device=device)
+        params = torch.load(normalizer_params_path, weights_only=True, map_location="cpu")
+        x_uub, x_llb = params["x_normalizer_params"]
+        y_uub, _ = params["y_normalizer0u_params"]
+        _, y_llb = params["y_normalizer0l_params"]
+        cin_size, cout_size = 3, 3
+        self.x_normalizer = Normalizer_ts(method="-11", dim=0, params=(x_uub, x_llb))
+        self.y_normalizer = Normalizer_ts(method="-11", dim=0, params=(y_uub[:cout_size], y_llb[:cout_size]))
+        self._load_model(ckpt_path, cin_size, cout_size, device)
+        self.max_val = torch.from_numpy(np.load(max_val_path)).to(device)
+        self.min_val = torch.from_numpy(np.load(min_val_path)).to(device)
+        self.batch_size = batch_size
+
+    # the 10-sensor adjoint: the whole tape in memory (cfd_siren_tape_forward / _vjp)
     def forward_tape(self, data):
         return self.model.tape_forward(self.coords, self._rows(data), self.x_normalizer, self.y_normalizer)
 

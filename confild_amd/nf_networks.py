@@ -289,6 +289,72 @@ class SIRENAutodecoder_film(nn.Module):
                    "cfd_siren_tape_vjp")
         return gz
 
+    # -- dense masked DPS adjoint (K12: cfd_siren_dense_grad) ------------------------
+    DENSE_BACKWARD = {"sum": 0, "delta": 1}
+    DENSE_COMPUTE = {"auto": 0, "f32": 1}
+
+    def set_dense_form(self, backward="sum", compute="auto"):
+        """Forms of dense_grad (development: tools/dense_dps_bench.py and the tests; the
+        defaults are the shipped choice).  compute: "auto" -- the K9t split-f16 tape
+        kernels in split_f16 compute where they take the width, else the fp32 chain --
+        or "f32"; set_compute("f32") always keeps exact fp32.  backward: "sum" (tile
+        sums on chip) or "delta" (delta tape per chunk + column sums)."""
+        if backward not in self.DENSE_BACKWARD or compute not in self.DENSE_COMPUTE:
+            raise ValueError(f"dense form ({backward!r}, {compute!r}) not in {sorted(self.DENSE_BACKWARD)} x "
+                             f"{sorted(self.DENSE_COMPUTE)}")
+        self._dense_form = (backward, compute)
+        return self
+
+    def dense_grad(self, coords, latents, rows_per_sample, y, mask=None, x_normalizer=None, y_normalizer=None,
+                   budget=None):
+        """Masked residual norm of a dense measurement and its latent gradient, in
+        bounded memory: for R latent rows (R, L) at N points (N, d), sample b owning
+        rows [b T, (b+1) T) (T = rows_per_sample),
+            norms[b] = || y - mask * decode(coords, latents) ||_2,   g_z = d norms / d latents.
+        y: (T, N, c) shared by the samples or (R, N, c); mask: None, (N, c), (T, N, c) or
+        (R, N, c).  budget: bytes of workspace the call may plan for (None: the library
+        default); the result's bits do not depend on it.  Only '-11' normalisers (fused).
+        Returns (g_z (R, L), norms (R / T))."""
+        d, L, c = self.in_coord_features, self.in_latent_features, self.out_features
+        dev = latents.device
+        if dev.type != "cuda":
+            raise _lib.CfdError("SIREN dense_grad needs GPU tensors (the HIP path has no CPU fallback)")
+        cf = coords.reshape(-1, d).to(device=dev, dtype=torch.float32).contiguous()
+        lat = latents.detach().reshape(-1, L).to(torch.float32).contiguous()
+        N, R, T = cf.shape[0], lat.shape[0], int(rows_per_sample)
+        if T < 1 or R % T:
+            raise ValueError(f"rows_per_sample {T} does not divide the {R} latent rows")
+        cf, xmax, xmin, ymax, ymin, ystride, post = self._norm_args(cf, N, dev, x_normalizer, y_normalizer)
+        if post is not None or (x_normalizer is not None and xmax is None):
+            raise NotImplementedError("the SIREN latent gradient fuses '-11' normalisers only")
+        yv = y.detach().to(device=dev, dtype=torch.float32).contiguous()
+        if yv.numel() not in (T * N * c, R * N * c):
+            raise ValueError(f"measurement of {yv.numel()} values matches neither one sample ({T * N * c}) nor the "
+                             f"batch ({R * N * c})")
+        y_rows = yv.numel() // (N * c)
+        mv, mask_rows = None, 0
+        if mask is not None:
+            mv = mask.detach().to(device=dev, dtype=torch.float32).contiguous()
+            mask_rows = mv.numel() // (N * c)
+            if mv.numel() != mask_rows * N * c or mask_rows not in (1, T, R):
+                raise ValueError(f"mask of {mv.numel()} values is not 1, {T} or {R} tables of ({N}, {c})")
+        h, lib = self._handle(dev), _lib.load()
+        bwd, comp = getattr(self, "_dense_form", ("sum", "auto"))
+        _lib.check(lib.cfd_siren_dense_set_form(h, self.DENSE_BACKWARD[bwd], self.DENSE_COMPUTE[comp]),
+                   "cfd_siren_dense_set_form")
+        budget = 0 if budget is None else int(budget)
+        n = C.c_size_t()
+        _lib.check(lib.cfd_siren_dense_workspace_bytes(h, N, R, budget, C.byref(n)), "siren dense workspace")
+        ws = torch.empty(max(n.value, 16), dtype=torch.uint8, device=dev)
+        self.dense_workspace_bytes = n.value   # what the last call allocated
+        gz = torch.empty((R, L), dtype=torch.float32, device=dev)
+        norms = torch.empty((R // T,), dtype=torch.float32, device=dev)
+        _lib.check(lib.cfd_siren_dense_grad(h, _lib.ptr(cf), N, _lib.ptr(lat), R, T, _lib.ptr(xmax), _lib.ptr(xmin),
+                                            _lib.ptr(ymax), _lib.ptr(ymin), ystride, _lib.ptr(yv), y_rows,
+                                            _lib.ptr(mv), mask_rows, _lib.ptr(gz), _lib.ptr(norms), _lib.ptr(ws),
+                                            ws.numel(), budget, _lib.stream_of(dev)), "cfd_siren_dense_grad")
+        return gz, norms
+
     # -- training (K10: cfd_siren_train_grad; the loop is confild_amd.cnf_train) ----
     def param_keys(self):
         """Parameter keys in the library's flat-gradient order (cfd_siren_param_info)."""

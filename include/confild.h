@@ -292,6 +292,56 @@ int  cfd_siren_tape_vjp(cfd_siren* h, const float* g_out, int64_t Ns, int R,
                         const float* ymax, const float* ymin, int64_t y_stride,
                         float* g_latents, void* workspace, size_t ws_bytes, void* stream);
 
+/* Dense masked DPS adjoint (Case2 / Case3 operators: a whole field of N points,
+ * measurements.py:58-181): the masked residual norm and its latent gradient in
+ * one call whose workspace is bounded by `budget` and does not grow with N.
+ * For sample b owning rows [b T, (b+1) T), T = rows_per_sample:
+ *   norm[b]   = || y - m (.) A ||_2 over the sample's T N c values, A the value
+ *               cfd_siren_forward gives; g_latents (R, L) = d norm / d latents
+ *               (zero where the norm is zero, as cfd_dps_residual).
+ *   y:    y_rows tables of (N, c), y_rows = rows_per_sample (shared by the samples)
+ *         or R; row r reads table r % y_rows.
+ *   mask: NULL (all ones) or mask_rows in {1, rows_per_sample, R} tables of (N, c),
+ *         row r reads table r % mask_rows.
+ * The N points are walked in chunks of whole 64-point slabs (and, where even one
+ * slab of all R rows exceeds the budget, in blocks of rows): tape forward,
+ * residual, backward, per-slab sums added into D (R, (nh+1) H) in slab order;
+ * then g = (D . V) / norm.  The reduction tree is a function of N alone, so
+ * g_latents and norm do not depend on budget or on how many samples share the
+ * call.  budget = 0: the library default (CFD_DENSE_DEFAULT_BUDGET).  A budget
+ * too small for one slab of one row: CFD_EARG before any launch.
+ * cfd_siren_dense_plan: the same planner from a configuration alone (no device);
+ * also reports the points per chunk and rows per block it chose. */
+#define CFD_DENSE_SLAB 64
+#define CFD_DENSE_DEFAULT_BUDGET ((size_t)1 << 30)
+int  cfd_siren_dense_plan(const cfd_siren_cfg* cfg, int64_t N, int R, size_t budget, int bwd_form,
+                          int compute_form, size_t* bytes, int64_t* chunk_points, int* block_rows);
+int  cfd_siren_dense_workspace_bytes(const cfd_siren* h, int64_t N, int R, size_t budget, size_t* bytes);
+int  cfd_siren_dense_grad(cfd_siren* h, const float* coords, int64_t N,
+                          const float* latents, int R, int rows_per_sample,
+                          const float* xmax, const float* xmin,
+                          const float* ymax, const float* ymin, int64_t y_stride,
+                          const float* y, int y_rows,
+                          const float* mask, int mask_rows,
+                          float* g_latents, float* norm,
+                          void* workspace, size_t ws_bytes, size_t budget, void* stream);
+/* Forms of the dense adjoint (development: tools/dense_dps_bench.py times them,
+ * profiles/dense_dps.json; the defaults are the shipped choice):
+ * compute   CFD_DENSE_COMPUTE_AUTO (default): the K9t split-f16 tape kernels for a
+ *           handle in CFD_SIREN_SPLIT_F16 whose width they take (H = 128, 256, 384),
+ *           else the fp32 MFMA chain; _F32: the fp32 chain.  A handle in
+ *           CFD_SIREN_F32 always runs the exact fp32 chain.
+ * backward  CFD_DENSE_BWD_SUM (default): the deltas of a tile (16 points in K9t, 64
+ *           in the fp32 chain) are summed on chip and one (nh+1) H partial is stored
+ *           per tile; CFD_DENSE_BWD_DELTA: the chunk's deltas are stored per pair
+ *           and column-summed after.
+ * cfd_siren_dense_plan takes the same two forms (for a handle in split compute). */
+#define CFD_DENSE_BWD_SUM   0
+#define CFD_DENSE_BWD_DELTA 1
+#define CFD_DENSE_COMPUTE_AUTO  0
+#define CFD_DENSE_COMPUTE_F32   1
+int  cfd_siren_dense_set_form(cfd_siren* h, int bwd_form, int compute_form);
+
 /* ------------------------------------------------------------------------ */
 /* CNF autodecoder training (K10; N/scripts/train.py:334-416 _single_trainer:  */
 /* model(coords, latents(idx)) -> MSELoss -> loss.backward(), Adam steps).     */

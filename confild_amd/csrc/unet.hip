@@ -833,6 +833,11 @@ void run_vjp(const cfd_unet* h, const float* d_eps, float* d_x, int B, const std
         wbpart = ws.take(bcap);   // bias-gradient slices of the split product kernel
     }
     if (ws.dry) return;
+    // what the attention backward cannot run is refused here, before the first launch
+    // of the walk (launch_attention_bwd would refuse it half-way through)
+    for (size_t si = 0; si < h->steps.size(); ++si)
+        CFD_REQUIRE(h->steps[si].kind != cfd::Step::Attn || (recs[si].in.H * recs[si].in.W) % 16 == 0, CFD_ESHAPE,
+                    "attention backward needs T % 16 == 0");
     std::vector<size_t> goff;
     {
         size_t o = 0;

@@ -82,7 +82,20 @@ struct StepArgs {
     const SamplerCtl* ctl;         // native loop: (seed, counter, goff) from device memory, or null
 };
 
-__global__ void step_kernel(StepArgs a) {
+// Known-row replacement (step_kernel<true>): after the step's sample s,
+//   q = a_i * known + b_i * n2,  out = m * q + (1 - m) * s
+// with (a_i, b_i) = (sqrt(abar_prev[i]), sqrt(1 - abar_prev[i])) from `tab`.
+struct KnownArgs {
+    const float* known;   // (1 | B, n)
+    const float* mask;    // (1 | B, n), values in [0, 1]
+    int64_t known_bstride, mask_bstride;   // 0 (shared) or n
+    const float* tab;     // (n_t, 2)
+    const float* noise2;  // may be null -> Philox(seed, counter2)
+    uint64_t counter2;    // read from ctl->counter2 in the native loop
+};
+
+template <bool KNOWN>
+__global__ void step_kernel(StepArgs a, KnownArgs kn) {
 #pragma clang fp contract(off)
     const int64_t grp = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t base = grp * 4;
@@ -95,6 +108,17 @@ __global__ void step_kernel(StepArgs a) {
         Philox::normal4(a.ctl->seed, a.ctl->counter, a.ctl->goff + (uint64_t)grp, z);
     } else {
         Philox::normal4(a.seed, a.counter, a.goff + (uint64_t)grp, z);
+    }
+    float z2[4] = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (KNOWN) {
+        if (kn.noise2) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) z2[j] = (base + j < a.total) ? kn.noise2[base + j] : 0.f;
+        } else if (a.ctl) {
+            Philox::normal4(a.ctl->seed, a.ctl->counter2, a.ctl->goff + (uint64_t)grp, z2);
+        } else {
+            Philox::normal4(a.seed, kn.counter2, a.goff + (uint64_t)grp, z2);
+        }
     }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -118,6 +142,12 @@ __global__ void step_kernel(StepArgs a) {
             const float e2 = (c[CFD_COEF_SRA] * x - xs) / c[CFD_COEF_SRM1];
             const float mean = xs * c[CFD_COEF_SQRT_ABP] + c[CFD_COEF_DIR] * e2;
             out = mean + mask * c[CFD_COEF_SIGMA_DDIM] * z[j];
+        }
+        if constexpr (KNOWN) {
+            const int64_t e = i - b * a.n;
+            const float m = kn.mask[b * kn.mask_bstride + e];
+            const float q = kn.tab[t * 2] * kn.known[b * kn.known_bstride + e] + kn.tab[t * 2 + 1] * z2[j];
+            out = m * q + (1.0f - m) * out;
         }
         a.x_out[i] = out;
         if (a.xs_out) a.xs_out[i] = xs;
@@ -187,6 +217,88 @@ __global__ void dps_latent_grad_kernel(const float* __restrict__ coefs, int clip
     g_direct[i] = g * c[CFD_COEF_SRA];
 }
 
+// ---------------------------------------------------------------------------
+// 'inpainting' under 'ps' (measurements.py:40-56, A(x0) = mask * x0 on the latent
+// image): residual norm and the two latent-gradient links in one call, no SIREN.
+// Per sample: x0 as step_kernel's xs (the same expression), r = y - m * x0,
+// norm = ||r||_2 in float64.  The sum runs over fixed chunks of LR_CHUNK elements:
+// thread t of chunk c adds elements c * LR_CHUNK + t + 256 j (j ascending), the
+// 256 thread sums fold by halves, and the chunk partials add in chunk order -- a
+// function of n_per_sample alone, whatever B or the grid.  No atomics.
+// ---------------------------------------------------------------------------
+constexpr int LR_CHUNK = 4096;
+
+struct LatentResArgs {
+    const float* coefs;
+    const float* x;
+    const float* eps;
+    const int64_t* t;
+    const float* y;
+    const float* mask;
+    int64_t y_bstride, mask_bstride;
+    int64_t n;       // elements per sample
+    int clip;
+};
+
+__device__ __forceinline__ float latent_x0(const LatentResArgs& a, const float* c, int64_t i, bool* pass) {
+#pragma clang fp contract(off)
+    float xs = c[CFD_COEF_SRA] * a.x[i] - c[CFD_COEF_SRM1] * a.eps[i];
+    *pass = !a.clip || (xs >= -1.0f && xs <= 1.0f);
+    if (a.clip) xs = fminf(fmaxf(xs, -1.0f), 1.0f);
+    return xs;
+}
+
+// grid (chunks, B): partial[b * chunks + c] = sum of r^2 over chunk c of sample b
+__global__ __launch_bounds__(256) void dps_latent_partial_kernel(LatentResArgs a, double* __restrict__ partial) {
+#pragma clang fp contract(off)
+    const int64_t b = blockIdx.y;
+    const float* c = a.coefs + a.t[b] * CFD_NCOEF;
+    const int64_t lo = (int64_t)blockIdx.x * LR_CHUNK;
+    const int64_t hi = lo + LR_CHUNK < a.n ? lo + LR_CHUNK : a.n;
+    double s = 0.0;
+    for (int64_t e = lo + threadIdx.x; e < hi; e += 256) {
+        bool pass;
+        const float x0 = latent_x0(a, c, b * a.n + e, &pass);
+        const float r = a.y[b * a.y_bstride + e] - a.mask[b * a.mask_bstride + e] * x0;
+        s += (double)r * r;
+    }
+    __shared__ double red[256];
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) partial[b * gridDim.x + blockIdx.x] = red[0];
+}
+
+// grid (chunks, B): norm_b from the partials in chunk order, then
+// g = -m * (r / norm_b) (zero where the norm is 0, or where the clamp cut x0),
+// d_eps = -g * srm1, g_direct = g * sra   (as dps_latent_grad_kernel)
+__global__ __launch_bounds__(256) void dps_latent_residual_kernel(LatentResArgs a, const double* __restrict__ partial,
+                                                                  float* __restrict__ norm, float* __restrict__ d_eps,
+                                                                  float* __restrict__ g_direct) {
+#pragma clang fp contract(off)
+    const int64_t b = blockIdx.y;
+    const float* c = a.coefs + a.t[b] * CFD_NCOEF;
+    double s = 0.0;
+    for (unsigned k = 0; k < gridDim.x; ++k) s += partial[b * gridDim.x + k];
+    const float nb = (float)sqrt(s);
+    if (blockIdx.x == 0 && threadIdx.x == 0) norm[b] = nb;
+    const int64_t lo = (int64_t)blockIdx.x * LR_CHUNK;
+    const int64_t hi = lo + LR_CHUNK < a.n ? lo + LR_CHUNK : a.n;
+    for (int64_t e = lo + threadIdx.x; e < hi; e += 256) {
+        const int64_t i = b * a.n + e;
+        bool pass;
+        const float x0 = latent_x0(a, c, i, &pass);
+        const float m = a.mask[b * a.mask_bstride + e];
+        const float r = a.y[b * a.y_bstride + e] - m * x0;
+        const float g = (pass && nb > 0.f) ? -(m * (r / nb)) : 0.0f;
+        d_eps[i] = -g * c[CFD_COEF_SRM1];
+        g_direct[i] = g * c[CFD_COEF_SRA];
+    }
+}
+
 // x_t -= (d/dx_prev) * scale   (condition_methods.py:88)
 __global__ void dps_update_kernel(const float* __restrict__ sample, const float* __restrict__ g_direct,
                                   const float* __restrict__ g_unet, float scale, float* __restrict__ x_out,
@@ -210,6 +322,7 @@ __global__ void sampler_advance_kernel(SamplerCtl* ctl, const int64_t* __restric
     __syncthreads();
     if (threadIdx.x == 0) {
         ctl->counter = k;
+        ctl->counter2 = CFD_KNOWN_COUNTER + k;
         ctl->k = k + 1;
     }
 }
@@ -218,6 +331,7 @@ __global__ void sampler_set_kernel(SamplerCtl* ctl, uint64_t k, uint64_t seed, u
     if (threadIdx.x == 0) {
         ctl->k = k;
         ctl->counter = k;
+        ctl->counter2 = CFD_KNOWN_COUNTER + k;
         ctl->seed = seed;
         ctl->goff = goff;
     }
@@ -250,8 +364,18 @@ void launch_sched_step_ctl(const cfd_sched* s, int kind, int clip, float* x, con
                            const SamplerCtl* ctl, int64_t n_per_sample, int B, hipStream_t st) {
     StepArgs a{s->coefs, x, eps, t, nullptr, x, nullptr, n_per_sample, n_per_sample * B, 0, 0, 0, kind, clip, ctl};
     const int64_t groups = ceil_div(a.total, 4);
-    hipLaunchKernelGGL(step_kernel, dim3((unsigned)ceil_div(groups, 256)), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(step_kernel<false>, dim3((unsigned)ceil_div(groups, 256)), dim3(256), 0, st, a, KnownArgs{});
     check_launch("step_kernel");
+}
+
+void launch_sched_step_known_ctl(const cfd_sched* s, int kind, int clip, float* x, const float* eps, const int64_t* t,
+                                 const SamplerCtl* ctl, const float* known, const float* mask, const float* table,
+                                 int64_t n_per_sample, int B, hipStream_t st) {
+    StepArgs a{s->coefs, x, eps, t, nullptr, x, nullptr, n_per_sample, n_per_sample * B, 0, 0, 0, kind, clip, ctl};
+    KnownArgs kn{known, mask, n_per_sample, n_per_sample, table, nullptr, 0};
+    const int64_t groups = ceil_div(a.total, 4);
+    hipLaunchKernelGGL(step_kernel<true>, dim3((unsigned)ceil_div(groups, 256)), dim3(256), 0, st, a, kn);
+    check_launch("step_kernel<known>");
 }
 }  // namespace cfd
 
@@ -285,9 +409,33 @@ extern "C" int cfd_sched_step(const cfd_sched* s, int kind, int clip, const floa
         cfd::StepArgs a{s->coefs, x, eps, t, noise, x_out, xstart_out, n_per_sample, n_per_sample * B,
                         seed, counter, offset / 4, kind, clip, nullptr};
         const int64_t groups = cfd::ceil_div(a.total, 4);
-        hipLaunchKernelGGL(cfd::step_kernel, dim3((unsigned)cfd::ceil_div(groups, 256)), dim3(256), 0,
-                           (hipStream_t)stream, a);
+        hipLaunchKernelGGL(cfd::step_kernel<false>, dim3((unsigned)cfd::ceil_div(groups, 256)), dim3(256), 0,
+                           (hipStream_t)stream, a, cfd::KnownArgs{});
         cfd::check_launch("step_kernel");
+    });
+}
+
+extern "C" int cfd_sched_step_known(const cfd_sched* s, int kind, int clip, const float* x, const float* eps,
+                                    const int64_t* t, const float* noise, uint64_t seed, uint64_t counter,
+                                    uint64_t offset, float* x_out, float* xstart_out, int64_t n_per_sample, int B,
+                                    const float* known, int64_t known_bstride, const float* mask,
+                                    int64_t mask_bstride, const float* table, const float* noise2, uint64_t counter2,
+                                    void* stream) {
+    return cfd::guard([&] {
+        CFD_REQUIRE(s && x && eps && t && x_out && known && mask && table, CFD_EARG, "null argument");
+        CFD_REQUIRE(offset % 4 == 0, CFD_EARG, "noise offset must be a multiple of 4");
+        CFD_REQUIRE(kind == CFD_STEP_DDPM || kind == CFD_STEP_DDIM, CFD_EARG, "unknown step kind");
+        CFD_REQUIRE(n_per_sample > 0 && B > 0, CFD_EARG, "empty step");
+        CFD_REQUIRE((known_bstride == 0 || known_bstride == n_per_sample) &&
+                        (mask_bstride == 0 || mask_bstride == n_per_sample),
+                    CFD_EARG, "known rows and mask must be shared (stride 0) or per sample (stride n)");
+        cfd::StepArgs a{s->coefs, x, eps, t, noise, x_out, xstart_out, n_per_sample, n_per_sample * B,
+                        seed, counter, offset / 4, kind, clip, nullptr};
+        cfd::KnownArgs kn{known, mask, known_bstride, mask_bstride, table, noise2, counter2};
+        const int64_t groups = cfd::ceil_div(a.total, 4);
+        hipLaunchKernelGGL(cfd::step_kernel<true>, dim3((unsigned)cfd::ceil_div(groups, 256)), dim3(256), 0,
+                           (hipStream_t)stream, a, kn);
+        cfd::check_launch("step_kernel<known>");
     });
 }
 
@@ -337,6 +485,37 @@ extern "C" int cfd_dps_latent_grad(const cfd_sched* s, int clip, const float* x,
                            (hipStream_t)stream, s->coefs, clip, x, eps, t, g_z, vmax, vmin, period, d_eps, g_direct,
                            n_per_sample, total);
         cfd::check_launch("dps_latent_grad_kernel");
+    });
+}
+
+extern "C" int cfd_dps_latent_residual_workspace_bytes(int64_t n_per_sample, int B, size_t* bytes) {
+    return cfd::guard([&] {
+        CFD_REQUIRE(bytes && n_per_sample > 0 && B > 0, CFD_EARG, "bad argument");
+        *bytes = sizeof(double) * (size_t)cfd::ceil_div(n_per_sample, (int64_t)cfd::LR_CHUNK) * (size_t)B;
+    });
+}
+
+extern "C" int cfd_dps_latent_residual(const cfd_sched* s, int clip, const float* x, const float* eps,
+                                       const int64_t* t, const float* y, int64_t y_bstride, const float* mask,
+                                       int64_t mask_bstride, float* norm, float* d_eps, float* g_direct,
+                                       int64_t n_per_sample, int B, void* workspace, size_t ws_bytes, void* stream) {
+    return cfd::guard([&] {
+        CFD_REQUIRE(s && x && eps && t && y && mask && norm && d_eps && g_direct && workspace, CFD_EARG,
+                    "null argument");
+        CFD_REQUIRE(n_per_sample > 0 && B > 0 && B <= 65535, CFD_EARG, "batch outside 1..65535");
+        CFD_REQUIRE((y_bstride == 0 || y_bstride == n_per_sample) && (mask_bstride == 0 || mask_bstride == n_per_sample),
+                    CFD_EARG, "measurement and mask must be shared (stride 0) or per sample (stride n)");
+        const int64_t chunks = cfd::ceil_div(n_per_sample, (int64_t)cfd::LR_CHUNK);
+        CFD_REQUIRE(ws_bytes >= sizeof(double) * (size_t)chunks * (size_t)B, CFD_EARG, "workspace too small");
+        CFD_REQUIRE(((uintptr_t)workspace & 7) == 0, CFD_EARG, "workspace must be 8-byte aligned");
+        cfd::LatentResArgs a{s->coefs, x, eps, t, y, mask, y_bstride, mask_bstride, n_per_sample, clip};
+        const dim3 grid((unsigned)chunks, (unsigned)B);
+        hipLaunchKernelGGL(cfd::dps_latent_partial_kernel, grid, dim3(256), 0, (hipStream_t)stream, a,
+                           (double*)workspace);
+        cfd::check_launch("dps_latent_partial_kernel");
+        hipLaunchKernelGGL(cfd::dps_latent_residual_kernel, grid, dim3(256), 0, (hipStream_t)stream, a,
+                           (const double*)workspace, norm, d_eps, g_direct);
+        cfd::check_launch("dps_latent_residual_kernel");
     });
 }
 

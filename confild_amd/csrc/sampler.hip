@@ -36,28 +36,43 @@ struct cfd_sampler {
     // is a kernel argument; set_compute changes the kernels)
     hipGraphExec_t exec[2] = {nullptr, nullptr};
     uint64_t exec_version = ~uint64_t(0);
+    // known-row replacement (cfd_sampler_set_known): buffers the sampler owns, since
+    // the graphs capture their addresses; the conditioned step has graphs of its own
+    // (kexec: one step, `unroll` steps), so switching it on or off re-captures nothing
+    float* known = nullptr;         // (B, n_per_sample)
+    float* kmask = nullptr;         // (B, n_per_sample)
+    float* ktab = nullptr;          // (n_t, 2)
+    int has_known = 0;
+    hipGraphExec_t kexec[2] = {nullptr, nullptr};
+    uint64_t captures = 0;          // graph captures so far (cfd_sampler_captures)
 };
 
 namespace {
 
 void destroy_graphs(cfd_sampler* sp) {
-    for (auto& e : sp->exec)
-        if (e) {
-            (void)hipGraphExecDestroy(e);
-            e = nullptr;
-        }
+    for (auto* set : {sp->exec, sp->kexec})
+        for (int i = 0; i < 2; ++i)
+            if (set[i]) {
+                (void)hipGraphExecDestroy(set[i]);
+                set[i] = nullptr;
+            }
     sp->exec_version = ~uint64_t(0);
 }
 
 // one reverse step on `st`: advance the timesteps, eps = U-Net(x, t), x = step(x, eps)
-void enqueue_step(const cfd_sampler* sp, hipStream_t st) {
+void enqueue_step(const cfd_sampler* sp, bool known, hipStream_t st) {
     cfd::launch_sampler_advance(sp->ctl, sp->tseq, sp->tseq + sp->n_steps, sp->tbuf, sp->tbuf + sp->B, sp->B, st);
     cfd::unet_forward_raw(sp->unet, sp->x, sp->tbuf + sp->B, sp->eps, sp->B, sp->ws, st);
-    cfd::launch_sched_step_ctl(sp->sched, sp->kind, sp->clip, sp->x, sp->eps, sp->tbuf, sp->ctl, sp->n_per_sample,
-                               sp->B, st);
+    if (known)
+        cfd::launch_sched_step_known_ctl(sp->sched, sp->kind, sp->clip, sp->x, sp->eps, sp->tbuf, sp->ctl, sp->known,
+                                         sp->kmask, sp->ktab, sp->n_per_sample, sp->B, st);
+    else
+        cfd::launch_sched_step_ctl(sp->sched, sp->kind, sp->clip, sp->x, sp->eps, sp->tbuf, sp->ctl,
+                                   sp->n_per_sample, sp->B, st);
 }
 
-hipGraphExec_t capture(const cfd_sampler* sp, int steps) {
+hipGraphExec_t capture(cfd_sampler* sp, bool known, int steps) {
+    ++sp->captures;
     hipStream_t cs;
     CFD_HIP(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
     hipGraph_t g = nullptr;
@@ -65,7 +80,7 @@ hipGraphExec_t capture(const cfd_sampler* sp, int steps) {
     try {
         CFD_HIP(hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal));
         try {
-            for (int i = 0; i < steps; ++i) enqueue_step(sp, cs);
+            for (int i = 0; i < steps; ++i) enqueue_step(sp, known, cs);
         } catch (...) {
             hipGraph_t dummy = nullptr;
             (void)hipStreamEndCapture(cs, &dummy);
@@ -137,6 +152,9 @@ extern "C" void cfd_sampler_destroy(cfd_sampler* sp) {
     (void)hipFree(sp->tbuf);
     (void)hipFree(sp->ctl);
     (void)hipFree(sp->ws);
+    (void)hipFree(sp->known);
+    (void)hipFree(sp->kmask);
+    (void)hipFree(sp->ktab);
     delete sp;
 }
 
@@ -164,19 +182,60 @@ extern "C" int cfd_sampler_run(cfd_sampler* sp, const float* x_in, float* x_out,
         if (x_in) CFD_HIP(hipMemcpyAsync(sp->x, x_in, bytes, hipMemcpyDeviceToDevice, st));
         cfd::launch_sampler_set(sp->ctl, (uint64_t)k0, seed, offset / 4, st);
         int k = k0;
+        const bool known = sp->has_known != 0;
         if (sp->graph) {
             if (sp->exec_version != cfd::unet_version(sp->unet)) {
                 destroy_graphs(sp);
-                sp->exec[0] = capture(sp, 1);
-                if (sp->unroll > 1) sp->exec[1] = capture(sp, sp->unroll);
                 sp->exec_version = cfd::unet_version(sp->unet);
             }
-            for (; sp->unroll > 1 && k + sp->unroll <= k1; k += sp->unroll) CFD_HIP(hipGraphLaunch(sp->exec[1], st));
-            for (; k < k1; ++k) CFD_HIP(hipGraphLaunch(sp->exec[0], st));
+            hipGraphExec_t* ex = known ? sp->kexec : sp->exec;
+            if (!ex[0]) {
+                // the plain and the conditioned step are captured when first run
+                ex[0] = capture(sp, known, 1);
+                if (sp->unroll > 1) ex[1] = capture(sp, known, sp->unroll);
+            }
+            for (; sp->unroll > 1 && k + sp->unroll <= k1; k += sp->unroll) CFD_HIP(hipGraphLaunch(ex[1], st));
+            for (; k < k1; ++k) CFD_HIP(hipGraphLaunch(ex[0], st));
         } else {
-            for (; k < k1; ++k) enqueue_step(sp, st);
+            for (; k < k1; ++k) enqueue_step(sp, known, st);
         }
         if (x_out) CFD_HIP(hipMemcpyAsync(x_out, sp->x, bytes, hipMemcpyDeviceToDevice, st));
+    });
+}
+
+extern "C" int cfd_sampler_set_known(cfd_sampler* sp, const float* known, int64_t known_bstride, const float* mask,
+                                     int64_t mask_bstride, const float* table, void* stream) {
+    return cfd::guard([&] {
+        CFD_REQUIRE(sp, CFD_EARG, "null sampler");
+        if (!known) {
+            sp->has_known = 0;   // the buffers and the conditioned graphs stay for the next set
+            return;
+        }
+        CFD_REQUIRE(mask && table, CFD_EARG, "known rows need a mask and the (n_t, 2) table");
+        const int64_t n = sp->n_per_sample;
+        CFD_REQUIRE((known_bstride == 0 || known_bstride == n) && (mask_bstride == 0 || mask_bstride == n), CFD_EARG,
+                    "known rows and mask must be shared (stride 0) or per sample (stride n)");
+        cfd::DeviceGuard dg(sp->device);
+        const hipStream_t st = (hipStream_t)stream;
+        const size_t row = sizeof(float) * (size_t)n, tab = sizeof(float) * 2 * (size_t)cfd::sched_nt(sp->sched);
+        if (!sp->known) CFD_HIP(hipMalloc(&sp->known, row * sp->B));
+        if (!sp->kmask) CFD_HIP(hipMalloc(&sp->kmask, row * sp->B));
+        if (!sp->ktab) CFD_HIP(hipMalloc(&sp->ktab, tab));
+        for (int b = 0; b < sp->B; ++b) {
+            CFD_HIP(hipMemcpyAsync(sp->known + (size_t)b * n, known + (size_t)b * known_bstride, row,
+                                   hipMemcpyDeviceToDevice, st));
+            CFD_HIP(hipMemcpyAsync(sp->kmask + (size_t)b * n, mask + (size_t)b * mask_bstride, row,
+                                   hipMemcpyDeviceToDevice, st));
+        }
+        CFD_HIP(hipMemcpyAsync(sp->ktab, table, tab, hipMemcpyDeviceToDevice, st));
+        sp->has_known = 1;
+    });
+}
+
+extern "C" int cfd_sampler_captures(const cfd_sampler* sp, uint64_t* n) {
+    return cfd::guard([&] {
+        CFD_REQUIRE(sp && n, CFD_EARG, "null argument");
+        *n = sp->captures;
     });
 }
 

@@ -15,7 +15,12 @@ struct SamplerCtl {
     uint64_t counter;  // Philox counter of the step being run (= its step number, as the Python loop's k)
     uint64_t seed;     // Philox key of this loop
     uint64_t goff;     // Philox group offset (= element offset of the shard / 4)
+    uint64_t counter2; // Philox counter of the step's known-row noise (= CFD_KNOWN_COUNTER + its step number)
 };
+
+// Philox counters: step k draws at k, the initial noise at 1 << 40, the noise
+// that carries known rows to the step's level at (1 << 41) + k.
+constexpr uint64_t CFD_KNOWN_COUNTER = uint64_t(1) << 41;
 
 // unet.hip: workspace size (cached per B) and the forward walk without the
 // per-call checks (the sampler checks once at creation).
@@ -38,5 +43,10 @@ void launch_sampler_set(SamplerCtl* ctl, uint64_t k, uint64_t seed, uint64_t gof
 // cfd_sched_step with the Philox (seed, counter, offset) read from ctl, in place on x
 void launch_sched_step_ctl(const cfd_sched* s, int kind, int clip, float* x, const float* eps, const int64_t* t,
                            const SamplerCtl* ctl, int64_t n_per_sample, int B, hipStream_t st);
+// the same step followed by the known-row replacement (cfd_sched_step_known), counter2 from ctl;
+// known and mask are per sample (B, n_per_sample), table is (n_t, 2)
+void launch_sched_step_known_ctl(const cfd_sched* s, int kind, int clip, float* x, const float* eps, const int64_t* t,
+                                 const SamplerCtl* ctl, const float* known, const float* mask, const float* table,
+                                 int64_t n_per_sample, int B, hipStream_t st);
 
 }  // namespace cfd

@@ -6,6 +6,13 @@ Host side: the float64 coefficient tables exactly as the reference builds them
 reverse step is one U-Net forward (cfd_unet_forward) plus one fused epilogue
 launch (cfd_sched_step: x0 prediction, clamp, posterior mean, noise).
 
+Known rows: every sampling call takes ``known`` / ``known_mask`` ((1 | B, 1, T, L),
+mask values in [0, 1]).  Each step then replaces its sample s by
+m * (a_i known + b_i n2) + (1 - m) * s, the known values at the noise level of the
+state the step produces (cfd_sched_step_known); at the last step the masked
+entries are ``known`` itself.  n2 is Philox (seed, (1 << 41) + k), or
+``known_noise`` (one tensor per step) in the Python loop.
+
 RNG: by default the per-step normals come from the in-kernel Philox stream keyed
 by a seed drawn from torch's default CPU generator at loop start (so
 ``torch.manual_seed`` makes runs reproducible).  For parity with a reference run,
@@ -90,6 +97,47 @@ def fresh_seed(noise, seed):
     return int(seed)
 
 
+# Philox counter of the known-row noise of step k: KNOWN_COUNTER + k (csrc/sampler.hpp)
+KNOWN_COUNTER = 1 << 41
+
+
+def broadcast_rows(v, B, tail, device, what):
+    """``v`` as a contiguous fp32 (1 | B, *tail) tensor on ``device`` and its batch
+    stride in elements (0: shared by the batch); ValueError for any other shape."""
+    v = torch.as_tensor(v).detach().to(device=device, dtype=torch.float32)
+    tail = tuple(tail)
+    if v.dim() > len(tail) + 1:
+        raise ValueError(f"{what} of shape {tuple(v.shape)} has more than {len(tail) + 1} dimensions")
+    lead = v.shape[0] if v.dim() == len(tail) + 1 else 1
+    if lead not in (1, B):
+        raise ValueError(f"{what} of shape {tuple(v.shape)} broadcasts to neither {(1,) + tail} nor {(B,) + tail}")
+    try:
+        v = torch.broadcast_to(v, (lead,) + tail)
+    except RuntimeError as e:
+        raise ValueError(f"{what} of shape {tuple(v.shape)} broadcasts to neither {(1,) + tail} nor "
+                         f"{(B,) + tail}") from e
+    return v.contiguous(), (0 if lead == 1 else int(np.prod(tail)))
+
+
+class _Known:
+    """Known rows of one sampling call on the device: values, mask, batch strides."""
+
+    def __init__(self, known, known_mask, shape, device):
+        if known is None or known_mask is None:
+            raise ValueError("known and known_mask go together")
+        B, tail = shape[0], tuple(shape[1:])
+        self.known, self.kstride = broadcast_rows(known, B, tail, device, "known")
+        self.mask, self.mstride = broadcast_rows(known_mask, B, tail, device, "known_mask")
+
+    @staticmethod
+    def of(known, known_mask, known_noise, shape, device):
+        if known is None and known_mask is None:
+            if known_noise is not None:
+                raise ValueError("known_noise without known rows")
+            return None
+        return _Known(known, known_mask, shape, device)
+
+
 class _Sched:
     """Device copy of one fp32 coefficient table (owns a cfd_sched handle)."""
 
@@ -121,6 +169,23 @@ class _NativeLoop:
         _lib.check(lib.cfd_sampler_create(handle, sched.handle, kind, 1 if clip else 0, B, n_per_sample, len(ti),
                                           ti.ctypes.data_as(C.c_void_p), tm.ctypes.data_as(C.c_void_p),
                                           1 if graph else 0, unroll, C.byref(self.handle)), "cfd_sampler_create")
+
+    def set_known(self, kn, table, device):
+        """Known rows (a _Known and the device (n_t, 2) table) for the following runs; None clears them."""
+        lib = _lib.load()
+        if kn is None:
+            _lib.check(lib.cfd_sampler_set_known(self.handle, None, 0, None, 0, None, _lib.stream_of(device)),
+                       "cfd_sampler_set_known")
+            return
+        _lib.check(lib.cfd_sampler_set_known(self.handle, _lib.ptr(kn.known), kn.kstride, _lib.ptr(kn.mask),
+                                             kn.mstride, _lib.ptr(table), _lib.stream_of(device)),
+                   "cfd_sampler_set_known")
+
+    def captures(self):
+        """Graph captures this loop has made so far."""
+        n = C.c_uint64()
+        _lib.check(_lib.load().cfd_sampler_captures(self.handle, C.byref(n)), "cfd_sampler_captures")
+        return int(n.value)
 
     def run(self, x_in, x_out, k0, k1, seed, offset, device):
         _lib.check(_lib.load().cfd_sampler_run(self.handle, _lib.ptr(x_in), _lib.ptr(x_out), k0, k1, seed, offset,
@@ -170,6 +235,7 @@ class GaussianDiffusion:
         self.posterior_mean_coef2 = (1.0 - self.alphas_cumprod_prev) * np.sqrt(alphas) / (1.0 - self.alphas_cumprod)
         self._scheds = {}
         self._natives = {}
+        self._ktabs = {}
 
     def _model_timesteps_host(self, indices):
         """Model timesteps of table indices (identity; SpacedDiffusion: timestep_map)."""
@@ -207,6 +273,21 @@ class GaussianDiffusion:
         tab[:, SIGMA_DDIM] = sigma
         return tab
 
+    def known_table(self) -> torch.Tensor:
+        """(num_timesteps, 2) fp32: sqrt(abar_prev), sqrt(1 - abar_prev), float64 tables
+        cast like coef_table's -- the level known rows are carried at after step i."""
+        f = lambda a: torch.from_numpy(np.asarray(a, dtype=np.float64)).float()  # noqa: E731
+        return torch.stack([f(np.sqrt(self.alphas_cumprod_prev)), f(np.sqrt(1.0 - self.alphas_cumprod_prev))],
+                           dim=1).contiguous()
+
+    def _ktab(self, device: torch.device):
+        dev = device.index if device.index is not None else torch.cuda.current_device()
+        t = self._ktabs.get(dev)
+        if t is None:
+            t = self.known_table().to(torch.device("cuda", dev))
+            self._ktabs[dev] = t
+        return t
+
     def _sched(self, device: torch.device, eta: float):
         dev = device.index if device.index is not None else torch.cuda.current_device()
         key = (dev, float(eta))
@@ -222,7 +303,7 @@ class GaussianDiffusion:
             raise NotImplementedError(f"model_mean_type {self.model_mean_type} on the HIP path (CoNFiLD uses EPSILON)")
 
     def _step(self, kind, model, x, t, clip_denoised, denoised_fn, cond_fn, model_kwargs, noise, seed, counter, eta,
-              offset=0):
+              offset=0, kn=None, known_noise=None):
         self._check_mean_type()
         if denoised_fn is not None or cond_fn is not None:
             raise NotImplementedError("denoised_fn / cond_fn (use the DPS sampler for conditioning)")
@@ -241,6 +322,18 @@ class GaussianDiffusion:
             nz = noise.to(device=x.device, dtype=torch.float32).contiguous()
         sched = self._sched(x.device, eta)
         n = x[0].numel()
+        if kn is not None:
+            nz2 = None
+            if known_noise is not None:
+                nz2 = known_noise.to(device=x.device, dtype=torch.float32).contiguous()
+                if nz2.shape != x.shape:
+                    raise ValueError("known_noise must have the shape of x")
+            _lib.check(_lib.load().cfd_sched_step_known(
+                sched.handle, kind, 1 if clip_denoised else 0, _lib.ptr(x), _lib.ptr(eps), _lib.ptr(t), _lib.ptr(nz),
+                seed, counter, offset, _lib.ptr(out), _lib.ptr(xs), n, x.shape[0], _lib.ptr(kn.known), kn.kstride,
+                _lib.ptr(kn.mask), kn.mstride, _lib.ptr(self._ktab(x.device)), _lib.ptr(nz2),
+                KNOWN_COUNTER + counter, _lib.stream_of(x.device)), "cfd_sched_step_known")
+            return {"sample": out, "pred_xstart": xs}
         _lib.check(_lib.load().cfd_sched_step(sched.handle, kind, 1 if clip_denoised else 0, _lib.ptr(x),
                                               _lib.ptr(eps), _lib.ptr(t), _lib.ptr(nz), seed, counter, offset,
                                               _lib.ptr(out), _lib.ptr(xs), n, x.shape[0],
@@ -248,28 +341,30 @@ class GaussianDiffusion:
         return {"sample": out, "pred_xstart": xs}
 
     def p_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None,
-                 noise=None, seed=None, counter=0):
+                 noise=None, seed=None, counter=0, known=None, known_mask=None, known_noise=None):
         """gaussian_diffusion.py:395-439 (noise: explicit normals, else Philox(seed, counter);
         with neither, a fresh seed per call from torch's generator, like the
         reference's fresh ``randn_like`` at :430)."""
         seed = fresh_seed(noise, seed)
         t = t.to(device=x.device, dtype=torch.int64).contiguous()
+        kn = _Known.of(known, known_mask, known_noise, x.shape, x.device)
         with torch.no_grad():
             return self._step(STEP_DDPM, model, x, t, clip_denoised, denoised_fn, cond_fn, model_kwargs, noise,
-                              seed, counter, 0.0)
+                              seed, counter, 0.0, kn=kn, known_noise=known_noise)
 
     def ddim_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None,
-                    eta=0.0, noise=None, seed=None, counter=0):
+                    eta=0.0, noise=None, seed=None, counter=0, known=None, known_mask=None, known_noise=None):
         """gaussian_diffusion.py:537-585 (noise / seed as p_sample)."""
         seed = fresh_seed(noise, seed)
         t = t.to(device=x.device, dtype=torch.int64).contiguous()
+        kn = _Known.of(known, known_mask, known_noise, x.shape, x.device)
         with torch.no_grad():
             return self._step(STEP_DDIM, model, x, t, clip_denoised, denoised_fn, cond_fn, model_kwargs, noise,
-                              seed, counter, eta)
+                              seed, counter, eta, kn=kn, known_noise=known_noise)
 
     # -- loops ------------------------------------------------------------------
     def _loop(self, kind, model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, device,
-              progress, eta, step_noise, seed, sample_offset=0):
+              progress, eta, step_noise, seed, sample_offset=0, known=None, known_mask=None, known_noise=None):
         if device is None:
             try:
                 device = next(model.parameters()).device
@@ -280,6 +375,7 @@ class GaussianDiffusion:
             raise _lib.CfdError("the HIP sampler runs on the GPU only; move the model to a HIP device")
         assert isinstance(shape, (tuple, list))
         lib = _lib.lib()
+        kn = _Known.of(known, known_mask, known_noise, shape, device)
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
         per_sample = int(np.prod(shape[1:]))
@@ -302,9 +398,10 @@ class GaussianDiffusion:
         for k, i in enumerate(indices):
             t = ts[i:i + 1].expand(B).contiguous()
             nz = None if step_noise is None else step_noise[k]
+            nz2 = None if known_noise is None else known_noise[k]
             with torch.no_grad():
                 out = self._step(kind, model, img, t, clip_denoised, denoised_fn, cond_fn, model_kwargs, nz,
-                                 seed, k, eta, offset)
+                                 seed, k, eta, offset, kn=kn, known_noise=nz2)
             if (k + 1) % RANGE_CHECK_EVERY == 0 or k == len(indices) - 1:
                 check_model_range(model, device)   # every RANGE_CHECK_EVERY steps: one stream sync
             yield out
@@ -317,12 +414,14 @@ class GaussianDiffusion:
         if callable(fn):
             fn(device)
 
-    def _native_ok(self, model, denoised_fn, cond_fn, model_kwargs, step_noise, progress):
+    def _native_ok(self, model, denoised_fn, cond_fn, model_kwargs, step_noise, progress, known_noise=None):
         from .unet import UNetModel
         return (NATIVE_MODE > 0 and isinstance(model, UNetModel) and denoised_fn is None and cond_fn is None
-                and not model_kwargs and step_noise is None and not progress and not self.rescale_timesteps)
+                and not model_kwargs and step_noise is None and known_noise is None and not progress
+                and not self.rescale_timesteps)
 
-    def _native_loop(self, kind, model, shape, noise, clip_denoised, device, eta, seed, sample_offset):
+    def _native_loop(self, kind, model, shape, noise, clip_denoised, device, eta, seed, sample_offset, known=None,
+                     known_mask=None):
         """The whole reverse loop on the device (csrc/sampler.hip): bit-identical to
         _loop with Philox noise, without per-step host work."""
         self._check_mean_type()
@@ -341,6 +440,7 @@ class GaussianDiffusion:
             raise ValueError("sharded sampling needs (elements per sample * first sample) % 4 == 0")
         if tuple(shape[1:]) != (model.in_channels, model.image_size, model.image_size):
             raise ValueError(f"shape {tuple(shape)} does not match the model's input")
+        kn = _Known.of(known, known_mask, None, shape, device)
         if noise is not None:
             img = noise.to(device=device, dtype=torch.float32).contiguous()
         else:
@@ -362,6 +462,8 @@ class GaussianDiffusion:
             self._natives[key] = nl
         out = torch.empty_like(img)
         self._clear_range_flag(model, device)
+        # known rows are copied into the loop's own buffers (or cleared) on every call
+        nl.set_known(kn, None if kn is None else self._ktab(device), device)
         n = self.num_timesteps
         for k0 in range(0, n, RANGE_CHECK_EVERY):
             k1 = min(n, k0 + RANGE_CHECK_EVERY)
@@ -369,46 +471,55 @@ class GaussianDiffusion:
             check_model_range(model, device)
         return out
 
+    def native_captures(self):
+        """Graph captures made so far by the native loops this object holds."""
+        return sum(nl.captures() for nl in self._natives.values())
+
     def p_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
-                      model_kwargs=None, device=None, progress=False, step_noise=None, seed=None, sample_offset=0):
+                      model_kwargs=None, device=None, progress=False, step_noise=None, seed=None, sample_offset=0,
+                      known=None, known_mask=None, known_noise=None):
         """gaussian_diffusion.py:441-485.  ``sample_offset``: index of this call's first
         sample in a larger (sharded) batch, so the Philox noise equals the unsharded run's.
         With Philox noise and a HIP UNetModel the loop runs natively (one HIP graph
         per step, csrc/sampler.hip); explicit step_noise / progress use the Python loop."""
-        if self._native_ok(model, denoised_fn, cond_fn, model_kwargs, step_noise, progress):
-            return self._native_loop(STEP_DDPM, model, shape, noise, clip_denoised, device, 0.0, seed, sample_offset)
+        if self._native_ok(model, denoised_fn, cond_fn, model_kwargs, step_noise, progress, known_noise):
+            return self._native_loop(STEP_DDPM, model, shape, noise, clip_denoised, device, 0.0, seed, sample_offset,
+                                     known, known_mask)
         final = None
         for s in self.p_sample_loop_progressive(model, shape, noise, clip_denoised, denoised_fn, cond_fn,
-                                                model_kwargs, device, progress, step_noise, seed, sample_offset):
+                                                model_kwargs, device, progress, step_noise, seed, sample_offset,
+                                                known, known_mask, known_noise):
             final = s
         return final["sample"]
 
     def p_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None,
                                   cond_fn=None, model_kwargs=None, device=None, progress=False, step_noise=None,
-                                  seed=None, sample_offset=0):
+                                  seed=None, sample_offset=0, known=None, known_mask=None, known_noise=None):
         """gaussian_diffusion.py:487-535."""
         yield from self._loop(STEP_DDPM, model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs,
-                              device, progress, 0.0, step_noise, seed, sample_offset)
+                              device, progress, 0.0, step_noise, seed, sample_offset, known, known_mask, known_noise)
 
     def ddim_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
                          model_kwargs=None, device=None, progress=False, eta=0.0, step_noise=None, seed=None,
-                         sample_offset=0):
+                         sample_offset=0, known=None, known_mask=None, known_noise=None):
         """gaussian_diffusion.py:625-662 (native loop as p_sample_loop)."""
-        if self._native_ok(model, denoised_fn, cond_fn, model_kwargs, step_noise, progress):
-            return self._native_loop(STEP_DDIM, model, shape, noise, clip_denoised, device, eta, seed, sample_offset)
+        if self._native_ok(model, denoised_fn, cond_fn, model_kwargs, step_noise, progress, known_noise):
+            return self._native_loop(STEP_DDIM, model, shape, noise, clip_denoised, device, eta, seed, sample_offset,
+                                     known, known_mask)
         final = None
         for s in self.ddim_sample_loop_progressive(model, shape, noise, clip_denoised, denoised_fn, cond_fn,
                                                    model_kwargs, device, progress, eta, step_noise, seed,
-                                                   sample_offset):
+                                                   sample_offset, known, known_mask, known_noise):
             final = s
         return final["sample"]
 
     def ddim_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None,
                                      cond_fn=None, model_kwargs=None, device=None, progress=False, eta=0.0,
-                                     step_noise=None, seed=None, sample_offset=0):
+                                     step_noise=None, seed=None, sample_offset=0, known=None, known_mask=None,
+                                     known_noise=None):
         """gaussian_diffusion.py:664-707."""
         yield from self._loop(STEP_DDIM, model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs,
-                              device, progress, eta, step_noise, seed, sample_offset)
+                              device, progress, eta, step_noise, seed, sample_offset, known, known_mask, known_noise)
 
     # -- training (the diffusion TrainLoop's loss, U/src/gaussian_diffusion.py:188-206, :744-853) ---------
     def _train_coefs(self, t):

@@ -25,6 +25,13 @@ mask=mask)``, replaces the three SIREN / residual lines by one call,
 
     g_z, norm = cfd_siren_dense_grad(unnorm(x0), y, mask) (bounded workspace)
 
+InpaintingOperator (A(x0) = mask * x0 on the latent image, measurements.py:40-56)
+needs no decoder: the three SIREN lines and cfd_dps_latent_grad become
+
+    d_eps, g_direct, norm = cfd_dps_latent_residual(x, eps, y, mask)
+
+with ``mask`` (required) and the measurement broadcast to (1 | B, 1, T, L).
+
 Batches: the reference loop only runs one sample per call (its ``if t != 0``
 needs a one-element t; the notebook loops over samples).  Here a batch of B
 samples is B independent DPS chains -- one residual norm per sample -- so a
@@ -38,16 +45,17 @@ step; the unused q_sample draw of the noisy measurement is not needed).
 """
 from __future__ import annotations
 
+import ctypes as C
 import functools
 
 import torch
 
 from .. import _lib
-from ..gaussian_diffusion import (LossType, ModelMeanType, ModelVarType, STEP_DDIM, STEP_DDPM, check_model_range,
-                                  fresh_seed, get_named_beta_schedule)
+from ..gaussian_diffusion import (LossType, ModelMeanType, ModelVarType, STEP_DDIM, STEP_DDPM, broadcast_rows,
+                                  check_model_range, fresh_seed, get_named_beta_schedule)
 from ..respace import SpacedDiffusion, space_timesteps
 from .condition_methods import Identity, PosteriorSampling
-from .measurements import Case4Operator
+from .measurements import Case4Operator, InpaintingOperator
 
 __SAMPLER__ = {}
 
@@ -135,6 +143,22 @@ def _mask_tables(mask, op, B, T, N, c, dev):
     return torch.broadcast_to(m, (lead, N, c)).contiguous()
 
 
+class _LatentMask:
+    """An 'inpainting' run on the device: measurement and mask as (1 | B, n) tables with
+    their batch strides, and the float64 partial sums cfd_dps_latent_residual needs."""
+
+    def __init__(self, mask, measurement, x):
+        if mask is None:
+            raise ValueError("Require mask: the 'inpainting' operator needs partial(cond.conditioning, mask=mask)")
+        B, tail = x.shape[0], tuple(x.shape[1:])
+        self.mask, self.mstride = broadcast_rows(mask, B, tail, x.device, "mask")
+        self.y, self.ystride = broadcast_rows(measurement, B, tail, x.device, "measurement")
+        nbytes = C.c_size_t()
+        _lib.check(_lib.lib().cfd_dps_latent_residual_workspace_bytes(x[0].numel(), B, C.byref(nbytes)),
+                   "cfd_dps_latent_residual_workspace_bytes")
+        self.ws = torch.empty((nbytes.value + 7) // 8, dtype=torch.float64, device=x.device)
+
+
 class _GuidedSampler(SpacedDiffusion):
     _kind = STEP_DDPM
 
@@ -154,7 +178,7 @@ class _GuidedSampler(SpacedDiffusion):
         method, kw = _method_of(measurement_cond_fn)
         if x_start.device.type != "cuda":
             raise _lib.CfdError("the DPS sampler runs on the GPU only (no CPU fallback)")
-        mask = self._device_mask(method, kw, x_start)
+        mask = self._device_mask(method, kw, x_start, measurement)
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
         x = x_start.detach().to(torch.float32).contiguous().clone()
@@ -181,15 +205,23 @@ class _GuidedSampler(SpacedDiffusion):
         x = x.detach().to(torch.float32).contiguous().clone()
         dist = torch.zeros(x.shape[0], dtype=torch.float32, device=x.device)
         img, x0, sample = self._guided_step(model, x, index, measurement, method, noise, seed, counter,
-                                            sample_offset, dist, self._device_mask(method, kw, x))
+                                            sample_offset, dist, self._device_mask(method, kw, x, measurement))
         return {"sample": img, "pred_xstart": x0, "x_t": sample, "distance": dist}
 
     @staticmethod
-    def _device_mask(method, kw, x):
-        """The mask tables of a 'ps' run on x's device (once per loop, not per step)."""
+    def _device_mask(method, kw, x, measurement=None):
+        """The mask tables of a 'ps' run on x's device (once per loop, not per step); for
+        the 'inpainting' operator a _LatentMask (mask and measurement, shape-checked
+        before the first launch)."""
         if not isinstance(method, PosteriorSampling):
             return None
         op = method.operator
+        if isinstance(op, InpaintingOperator):
+            if x.device.type != "cuda":
+                raise _lib.CfdError("the DPS sampler runs on the GPU only (no CPU fallback)")
+            if x.dim() != 4 or x.shape[1] != 1:
+                raise ValueError(f"latents must be (B, 1, T, L), got {tuple(x.shape)}")
+            return _LatentMask(kw.get("mask"), measurement, x)
         return _mask_tables(kw.get("mask"), op, x.shape[0], x.shape[2], op.coords.shape[0], op.model.out_features,
                             x.device)
 
@@ -222,6 +254,19 @@ class _GuidedSampler(SpacedDiffusion):
         if not dps:
             return sample, x0, sample
         op = method.operator
+        if isinstance(mask, _LatentMask):
+            d_eps = torch.empty_like(x)
+            g_dir = torch.empty_like(x)
+            _lib.check(lib.cfd_dps_latent_residual(sched.handle, clip, _lib.ptr(x), _lib.ptr(eps), _lib.ptr(t),
+                                                   _lib.ptr(mask.y), mask.ystride, _lib.ptr(mask.mask), mask.mstride,
+                                                   _lib.ptr(dist_out), _lib.ptr(d_eps), _lib.ptr(g_dir), n, B,
+                                                   _lib.ptr(mask.ws), mask.ws.numel() * 8, st),
+                       "cfd_dps_latent_residual")
+            g_unet = model.input_vjp(d_eps)
+            img = torch.empty_like(x)
+            _lib.check(lib.cfd_dps_update(_lib.ptr(sample), _lib.ptr(g_dir), _lib.ptr(g_unet), float(method.scale),
+                                          _lib.ptr(img), x.numel(), st), "cfd_dps_update")
+            return img, x0, sample
         y = measurement.to(device=dev, dtype=torch.float32).contiguous()
         vmax, vmin = op._bounds()
         if n % vmax.numel():

@@ -52,6 +52,35 @@ class NonLinearOperator(ABC):
         return data + measurement - self.forward(data)
 
 
+@register_operator(name="inpainting")
+class InpaintingOperator(LinearOperator):
+    """measurements.py:40-56: A(x) = mask * x on the latent image itself (known rows
+    of a latent sequence, gaps, end states).  Plain torch, CPU tensors included;
+    under 'ps' the guided sampler runs its adjoint as one cfd_dps_latent_residual."""
+
+    def __init__(self, device):
+        self.device = device
+
+    def forward(self, data, **kwargs):
+        """mask * data on the operator's device; without a usable ``mask`` keyword the
+        reference's ValueError("Require mask")."""
+        mask = kwargs.get("mask")
+        if not torch.is_tensor(mask):
+            raise ValueError("Require mask")
+        try:
+            return mask.to(self.device) * data.to(self.device)
+        except RuntimeError as e:
+            raise ValueError("Require mask") from e
+
+    def transpose(self, data, **kwargs):
+        """A^T applied to a measurement: the identity, as in the reference (:52-53)."""
+        return data
+
+    def ortho_project(self, data, **kwargs):
+        """(I - A) data, the part of the image the mask hides (:55-56)."""
+        return data - self.forward(data, **kwargs)
+
+
 def _siren_dims(sd):
     n1 = sorted(int(k.split(".")[1]) for k in sd if k.startswith("net1.") and k.endswith(".weight"))
     first, last = sd["net1.0.weight"], sd[f"net1.{n1[-1]}.weight"]

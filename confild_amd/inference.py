@@ -13,6 +13,14 @@ reference-preserving defaults:
                                split-f16, fp32-level error; bf16 = config E, bf16
                                operands with fp32 accumulation, GroupNorm/softmax fp32)
   compute: split_f16 | fp32 | bf16   (explicit U-Net compute mode; overrides precision)
+  rollout_windows: 0          (reference: one window of time_length rows.  W > 0 continues
+                               every sample by W conditioned windows, confild_amd.rollout:
+                               T_total = T + W * (T - rollout_overlap) rows, saved as
+                               (B*T_total, N, c))
+  rollout_overlap: T // 2     (rows a window shares with the sequence before it)
+  rollout_method: replace | ps   (replace: known-row replacement in the native loop;
+                               ps: posterior sampling with the 'inpainting' operator)
+  rollout_scale: 1.0          (the 'ps' step size)
 Known deviation (fixed on purpose): ``channel_mult`` from the YAML IS passed to
 create_model (the reference reads but drops it, inference.py:38-44, so its own
 case4.yml raises ValueError).
@@ -64,6 +72,21 @@ def unet_compute(inp) -> str:
     return PRECISIONS[prec]
 
 
+def rollout_sampler(inp, diff, sampler):
+    """(diffusion, method) of a rollout run: ``diff`` for 'replace', for 'ps' a guided
+    sampler on the same schedule (fixed-large variance, clipped x0, as ``diff`` runs)."""
+    method = str(getattr(inp, "rollout_method", "replace"))
+    if method == "replace":
+        return diff, method
+    if method != "ps":
+        raise ValueError(f"rollout_method must be 'replace' or 'ps', got {method!r}")
+    from .guided.gaussian_diffusion import create_sampler
+    return create_sampler(sampler=sampler, steps=inp.steps, noise_schedule=inp.noise_schedule,
+                          model_mean_type="epsilon", model_var_type="fixed_large", dynamic_threshold=False,
+                          clip_denoised=True, rescale_timesteps=False,
+                          timestep_respacing=getattr(inp, "timestep_respacing", "")), method
+
+
 def run(yaml_path: str):
     rank, world, device = dist.init_from_env()
     if device.type != "cuda":
@@ -91,11 +114,25 @@ def run(yaml_path: str):
     sampler = getattr(inp, "sampler", "ddpm")
     B, T, L = inp.test_batch_size, inp.time_length, inp.latent_length
 
+    windows = int(getattr(inp, "rollout_windows", 0))
+    if windows < 0:
+        raise ValueError(f"rollout_windows must be >= 0, got {windows}")
+
     def sample(start, count):
+        if windows:
+            from .rollout import extend_latents
+            if (T, L) != (model.image_size, model.image_size):
+                raise ValueError("a rollout needs time_length == latent_length == image_size")
+            kind = "ddpm" if sampler == "ddpm" else "ddim"     # as the plain run picks its loop
+            rdiff, method = rollout_sampler(inp, diff, kind)
+            return extend_latents(model, rdiff, None, windows, int(getattr(inp, "rollout_overlap", T // 2)), method,
+                                  scale=float(getattr(inp, "rollout_scale", 1.0)), seed=loop_seed,
+                                  sample_offset=start, sampler=kind, batch_size=count)[:, 0]
         fn = diff.p_sample_loop if sampler == "ddpm" else diff.ddim_sample_loop
         return fn(model, (count, 1, T, L), seed=loop_seed, sample_offset=start)[:, 0]
 
     gen = dist.sharded_samples(sample, B)                    # (B, T, L) on every rank
+    T = gen.shape[1]                                         # T_total of a rollout
 
     max_val = torch.as_tensor(np.load(inp.max_val), dtype=torch.float32).to(device).contiguous()
     min_val = torch.as_tensor(np.load(inp.min_val), dtype=torch.float32).to(device).contiguous()

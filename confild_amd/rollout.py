@@ -1,0 +1,138 @@
+"""Latent sequences longer than the U-Net's ``time_length``: overlapping windows.
+
+A latent is an image (B, 1, T, L) whose rows are snapshots.  A rollout chains
+windows of T rows: window w >= 1 is sampled conditioned on its first ``overlap``
+rows, which are the last ``overlap`` rows of the sequence so far, and contributes
+its remaining T - overlap rows.  Two ways to condition (no reference
+counterpart for the driver; 'ps' + 'inpainting' is the reference's operator):
+
+  replace  known-row replacement inside the unconditioned loop
+           (GaussianDiffusion.p_sample_loop(known=, known_mask=), the native
+           graph loop included): one fused elementwise pass per step;
+  ps       posterior sampling with the 'inpainting' operator
+           (guided sampler): a U-Net forward and an input VJP per step.
+
+Window w draws from Philox key ``seed + w``; samples shard over ranks through
+``sample_offset`` exactly as the unconditioned loops do (dist.sharded_samples).
+"""
+from __future__ import annotations
+
+import functools
+
+import torch
+
+from . import _lib
+from .gaussian_diffusion import STEP_DDIM, GaussianDiffusion
+
+METHODS = ("replace", "ps")
+
+
+def plan_windows(T, overlap, n_windows):
+    """Row slices of every window in the stitched sequence (host only): window 0 is
+    slice(0, T); window w >= 1 starts ``overlap`` rows before the end of window
+    w - 1.  The sequence has T + n_windows * (T - overlap) rows."""
+    T, overlap, n_windows = int(T), int(overlap), int(n_windows)
+    if T < 1 or not 1 <= overlap < T:
+        raise ValueError(f"overlap must satisfy 1 <= overlap < T, got overlap {overlap}, T {T}")
+    if n_windows < 0:
+        raise ValueError(f"n_windows must be >= 0, got {n_windows}")
+    stride = T - overlap
+    return [slice(w * stride, w * stride + T) for w in range(n_windows + 1)]
+
+
+def window_noise(shape, seed, sample_offset, device):
+    """x_T of one window, as the unconditioned loops draw it: Philox (seed, 1 << 40)
+    at the shard's stream position."""
+    img = torch.empty(*shape, dtype=torch.float32, device=device)
+    offset = sample_offset * img[0].numel()
+    if offset % 4:
+        raise ValueError("sharded sampling needs (elements per sample * first sample) % 4 == 0")
+    _lib.check(_lib.lib().cfd_randn(_lib.ptr(img), img.numel(), seed, 1 << 40, offset, _lib.stream_of(device)),
+               "cfd_randn")
+    return img
+
+
+def known_rows(prev, overlap):
+    """(known, mask) of the window that follows ``prev`` (B, 1, T, L): its rows
+    [0, overlap) are the last ``overlap`` rows of prev, the mask (1, 1, T, L) is 1 there."""
+    T = prev.shape[2]
+    known = torch.zeros_like(prev)
+    known[:, :, :overlap] = prev[:, :, T - overlap:]
+    mask = torch.zeros(1, 1, T, prev.shape[3], dtype=torch.float32, device=prev.device)
+    mask[:, :, :overlap] = 1.0
+    return known, mask
+
+
+def _ps_method(device, scale):
+    from .guided.condition_methods import get_conditioning_method
+    from .guided.measurements import get_noise, get_operator
+    return get_conditioning_method("ps", get_operator("inpainting", device=device),
+                                   get_noise("gaussian", sigma=0.0), scale=scale)
+
+
+def sample_window(model, diffusion, shape, method, *, known=None, mask=None, scale=1.0, seed, sample_offset=0,
+                  sampler="ddpm", device=None):
+    """One window (B, 1, T, L): unconditioned when ``known`` is None, else conditioned on
+    ``known`` where ``mask`` is 1.  ``sampler`` picks the DDPM / DDIM loop for
+    'replace'; a guided sampler ('ps') carries its own kind."""
+    if method not in METHODS:
+        raise ValueError(f"method must be one of {METHODS}, got {method!r}")
+    if method == "replace":
+        if sampler not in ("ddpm", "ddim"):
+            raise ValueError(f"sampler must be 'ddpm' or 'ddim', got {sampler!r}")
+        fn = diffusion.p_sample_loop if sampler == "ddpm" else diffusion.ddim_sample_loop
+        return fn(model, tuple(shape), device=device, seed=seed, sample_offset=sample_offset, known=known,
+                  known_mask=mask)
+    from .guided.gaussian_diffusion import _GuidedSampler
+    if not isinstance(diffusion, _GuidedSampler):
+        raise TypeError("method 'ps' takes a guided sampler from confild_amd.guided.gaussian_diffusion.create_sampler")
+    if device is None:
+        device = next(model.parameters()).device
+    if known is None:
+        # window 0: the guided sampler's own schedule and step kind, no measurement
+        fn = GaussianDiffusion.ddim_sample_loop if diffusion._kind == STEP_DDIM else GaussianDiffusion.p_sample_loop
+        return fn(diffusion, model, tuple(shape), clip_denoised=diffusion.clip_denoised, device=device, seed=seed,
+                  sample_offset=sample_offset)
+    cond = _ps_method(device, scale)
+    x_T = window_noise(shape, seed, sample_offset, device)
+    return diffusion.p_sample_loop(model=model, x_start=x_T, measurement=mask * known,
+                                   measurement_cond_fn=functools.partial(cond.conditioning, mask=mask), seed=seed,
+                                   sample_offset=sample_offset)
+
+
+def extend_latents(model, diffusion, first, n_windows, overlap, method, *, scale=1.0, seed, sample_offset=0,
+                   sampler="ddpm", batch_size=1):
+    """(B, 1, T + n_windows * (T - overlap), L): ``first`` (B, 1, T, L) continued by
+    ``n_windows`` conditioned windows.  ``first=None`` samples window 0 unconditionally:
+    ``batch_size`` samples of the model's (1, image_size, image_size) input.
+
+    The stitched sequence keeps the earlier window's values on each overlap and
+    appends the later window's rows [overlap, T).  method 'replace' takes a
+    GaussianDiffusion, 'ps' a guided sampler (create_sampler) and ``scale``.
+    Window w uses Philox key seed + w."""
+    if method not in METHODS:
+        raise ValueError(f"method must be one of {METHODS}, got {method!r}")
+    if torch.is_tensor(first):
+        if first.dim() != 4 or first.shape[1] != 1:
+            raise ValueError(f"first must be (B, 1, T, L), got {tuple(first.shape)}")
+        seq = first.detach().to(torch.float32).contiguous()
+        device = seq.device
+        shape = tuple(seq.shape)
+    else:
+        if first is not None:
+            raise TypeError("first must be a (B, 1, T, L) tensor or None")
+        device = next(model.parameters()).device
+        shape = (int(batch_size), 1, model.image_size, model.image_size)
+        seq = None
+    T = shape[2]
+    plan_windows(T, overlap, n_windows)   # argument checks
+    seed = int(seed)
+    if seq is None:
+        seq = sample_window(model, diffusion, shape, method, seed=seed, sample_offset=sample_offset, sampler=sampler,
+                            device=device)
+    for w in range(1, n_windows + 1):
+        known, mask = known_rows(seq[:, :, -T:], overlap)
+        win = sample_window(model, diffusion, shape, method, known=known, mask=mask, scale=scale, seed=seed + w,
+                            sample_offset=sample_offset, sampler=sampler, device=device)
+        seq = torch.cat([seq, win[:, :, overlap:]], dim=2)
+    return seq

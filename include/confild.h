@@ -168,6 +168,23 @@ int  cfd_sched_step(const cfd_sched* s, int kind, int clip, const float* x, cons
                     const int64_t* t, const float* noise, uint64_t seed, uint64_t counter,
                     uint64_t offset, float* x_out, float* xstart_out, int64_t n_per_sample, int B,
                     void* stream);
+/* cfd_sched_step followed by known-row replacement (no reference counterpart; the
+ * cheap route of conditioning on known latent rows).  With s the step's sample
+ * at table index i, computed exactly as cfd_sched_step does:
+ *   q   = a_i * known + b_i * n2        a_i = sqrt(abar_prev[i]), b_i = sqrt(1 - abar_prev[i])
+ *   out = m * q + (1 - m) * s           (fp contraction off, in this order)
+ * so the known rows are carried at the noise level of the state the step
+ * produces; at i = 0, q = known.  m = 0 leaves s bit for bit, m = 1 gives q.
+ * known / mask: (n_per_sample) tables shared by the batch (stride 0) or per sample
+ * (stride n_per_sample).  table: (n_t, 2) device fp32 rows (a_i, b_i), float64
+ * tables cast to fp32 like host_coefs.  n2: noise2 (B*n device normals), or NULL
+ * for Philox (seed, counter2) at stream position offset + element; the loops use
+ * counter2 = (1 << 41) + k, apart from the step's k and the initial noise's 1 << 40. */
+int  cfd_sched_step_known(const cfd_sched* s, int kind, int clip, const float* x, const float* eps,
+                          const int64_t* t, const float* noise, uint64_t seed, uint64_t counter,
+                          uint64_t offset, float* x_out, float* xstart_out, int64_t n_per_sample, int B,
+                          const float* known, int64_t known_bstride, const float* mask, int64_t mask_bstride,
+                          const float* table, const float* noise2, uint64_t counter2, void* stream);
 /* Native reverse loop (p_sample_loop / ddim_sample_loop, gaussian_diffusion.py:
  * 441-535 / 625-707, with Philox noise): per step the timestep advance, the U-Net
  * forward and the K6 epilogue, with no host work between steps.  graph != 0
@@ -198,6 +215,17 @@ int  cfd_stream_create_cu_range(int device, int first_cu, int n_cu, void** strea
 int  cfd_stream_destroy(void* stream);
 int  cfd_sampler_run(cfd_sampler* sp, const float* x_in, float* x_out, int k0, int k1, uint64_t seed,
                      uint64_t offset, void* stream);
+/* Known rows for the following cfd_sampler_run calls: every step becomes
+ * cfd_sched_step_known with counter2 = (1 << 41) + k read from device memory.
+ * known, mask (strides 0 or n_per_sample) and table ((n_t, 2)) are device arrays,
+ * copied on `stream` into buffers the sampler owns (graphs capture addresses), so
+ * new contents need no re-capture.  The conditioned step has its own captured
+ * graphs next to the unconditioned ones; known == NULL clears it, and the runs
+ * that follow are the unconditioned loop, its graphs and its bits.
+ * cfd_sampler_captures: the number of graph captures the sampler has made. */
+int  cfd_sampler_set_known(cfd_sampler* sp, const float* known, int64_t known_bstride, const float* mask,
+                           int64_t mask_bstride, const float* table, void* stream);
+int  cfd_sampler_captures(const cfd_sampler* sp, uint64_t* n);
 /* n standard normals from Philox4x32-10 (seed, counter) at stream positions
  * offset .. offset+n-1 (offset % 4 == 0): the device-side stand-in for th.randn
  * (gaussian_diffusion.py:513). */
@@ -227,6 +255,24 @@ int  cfd_dps_latent_grad(const cfd_sched* s, int clip, const float* x, const flo
                          float* d_eps, float* g_direct, int64_t n_per_sample, int B, void* stream);
 int  cfd_dps_update(const float* sample, const float* g_direct, const float* g_unet, float scale,
                     float* x_out, int64_t n, void* stream);
+/* The 'inpainting' operator under 'ps' (measurements.py:40-56: A(x0) = mask * x0 on
+ * the latent image): what cfd_dps_residual and cfd_dps_latent_grad do for a SIREN
+ * operator, in one call and without a decoder.  Per sample b:
+ *   x0     = sra * x - srm1 * eps, clamped when clip (cfd_sched_step's pred_xstart, the same bits)
+ *   r      = y - m * x0,   norm[b] = ||r||_2
+ *   g      = -m * (r / norm[b]); zero where norm[b] == 0 and, with clip, where the
+ *            unclamped x0 lies outside [-1, 1]
+ *   d_eps  = -g * srm1,    g_direct = g * sra
+ * y / mask: (n_per_sample) tables shared by the batch (stride 0) or per sample
+ * (stride n_per_sample).  The norm is summed in float64 over fixed 4096-element
+ * chunks (one workgroup each) whose partials add in chunk order: the order is a
+ * function of n_per_sample alone, not of B or the grid, and there are no atomics.
+ * workspace: cfd_dps_latent_residual_workspace_bytes(n_per_sample, B), 8-byte aligned. */
+int  cfd_dps_latent_residual_workspace_bytes(int64_t n_per_sample, int B, size_t* bytes);
+int  cfd_dps_latent_residual(const cfd_sched* s, int clip, const float* x, const float* eps, const int64_t* t,
+                             const float* y, int64_t y_bstride, const float* mask, int64_t mask_bstride,
+                             float* norm, float* d_eps, float* g_direct, int64_t n_per_sample, int B,
+                             void* workspace, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------ */
 /* Conditional neural field decoder: SIRENAutodecoder_film                    */

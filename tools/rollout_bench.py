@@ -1,0 +1,121 @@
+"""Time one rollout window at config B's widths (64^2 latent, B = 8, 256 steps):
+
+  uncond/<parent build>   the unconditioned native loop on the parent commit's library
+  uncond                  the same loop on this build
+  replace                 the loop with known-row replacement (cfd_sched_step_known in the graph)
+  ps                      posterior sampling with the 'inpainting' operator (Python loop:
+                          U-Net forward with tape, cfd_dps_latent_residual, input VJP, update)
+
+    python tools/rollout_bench.py [--parent libconfild_hip_parent.so] [--rounds 3] [--out profiles/rollout.json]
+
+Each timing is a child process (CFD_LIB selects the in-tree build), the four run
+interleaved for ``--rounds`` rounds on the same device.  A child builds the
+synthetic cfgB64 U-Net, runs one whole window untimed (graph capture, first
+launches), then times ``--loops`` windows with a host clock around work that ends
+in a device synchronise.  The parent library lacks this change's symbols
+(_lib.load binds what a CFD_LIB build exports); its child leaves the known rows out.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+CHILD = r"""
+import ast, json, sys, time
+import numpy as np, torch
+sys.path.insert(0, sys.argv[1])
+mode, loops, steps, B = sys.argv[2], int(sys.argv[3]), sys.argv[4], int(sys.argv[5])
+from confild_amd import _lib, synth
+from confild_amd import gaussian_diffusion as gd
+if mode == "uncond_parent":
+    gd._NativeLoop.set_known = lambda self, kn, table, device: None   # the parent has no known rows to clear
+from confild_amd.script_util import create_gaussian_diffusion, create_model
+g = np.load(sys.argv[1] + "/tests/golden/unet_cfgB64.npz")
+kw = ast.literal_eval(str(g["kwargs"]))
+m = create_model(**kw)
+m.load_state_dict({k: torch.from_numpy(v) for k, v in
+                   synth.unet_state_dict(int(g["seed"]), {k: tuple(v.shape) for k, v in m.state_dict().items()}).items()})
+dev = torch.device("cuda", 0)
+m.to(dev)
+S = kw["image_size"]
+shape = (B, 1, S, S)
+known = torch.from_numpy(synth.uniform(1, "rb/known", shape, -0.9, 0.9)).to(dev)
+mask = torch.zeros(1, 1, S, S, device=dev)
+mask[:, :, :S // 2] = 1.0
+if mode == "ps":
+    from confild_amd import rollout
+    from confild_amd.guided.gaussian_diffusion import create_sampler
+    d = create_sampler(sampler="ddpm", steps=1000, noise_schedule="cosine", model_mean_type="epsilon",
+                       model_var_type="fixed_large", dynamic_threshold=False, clip_denoised=True,
+                       rescale_timesteps=False, timestep_respacing=steps)
+    run = lambda: rollout.sample_window(m, d, shape, "ps", known=known, mask=mask, scale=0.5, seed=3)
+else:
+    d = create_gaussian_diffusion(steps=1000, noise_schedule="cosine", timestep_respacing=steps)
+    kwargs = dict(known=known, known_mask=mask) if mode == "replace" else {}
+    run = lambda: d.p_sample_loop(m, shape, seed=3, **kwargs)
+out = run()
+torch.cuda.synchronize()
+assert torch.isfinite(out).all()
+ts = []
+for _ in range(loops):
+    t0 = time.perf_counter()
+    run()
+    torch.cuda.synchronize()
+    ts.append(time.perf_counter() - t0)
+n = d.num_timesteps
+print(json.dumps({"mode": mode, "lib": _lib.LIB_PATH.rsplit("/", 1)[-1], "steps": n, "B": B,
+                  "window_ms": [1e3 * t for t in ts], "ms_per_step": 1e3 * min(ts) / n}))
+"""
+
+
+def child(mode, lib, loops, steps, B):
+    env = dict(os.environ)
+    if lib:
+        env["CFD_LIB"] = lib
+    else:
+        env.pop("CFD_LIB", None)
+    p = subprocess.run([sys.executable, "-c", CHILD, ROOT, mode, str(loops), steps, str(B)], env=env,
+                       capture_output=True, text=True, timeout=600)
+    if p.returncode != 0:
+        raise SystemExit(f"{mode} ({lib or 'default library'}) failed with {p.returncode}:\n{p.stderr[-2000:]}")
+    return json.loads(p.stdout.strip().splitlines()[-1])
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--parent", default="libconfild_hip_parent.so",
+                    help="the parent commit's build under confild_amd/lib (make VARIANT=parent in its checkout)")
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--loops", type=int, default=3)
+    ap.add_argument("--steps", default="256")
+    ap.add_argument("--batch", type=int, default=8)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    runs = [("uncond_parent", a.parent), ("uncond", None), ("replace", None), ("ps", None)]
+    res = {mode: [] for mode, _ in runs}
+    for r in range(a.rounds):
+        for mode, lib in runs:
+            loops = 1 if mode == "ps" else a.loops
+            one = child(mode, lib, loops, a.steps, a.batch)
+            res[mode].append(one)
+            print(f"round {r} {mode:14s} {one['ms_per_step']:.3f} ms/step", flush=True)
+    summary = {mode: {"ms_per_step": [x["ms_per_step"] for x in v]} for mode, v in res.items()}
+    doc = {"what": "one rollout window at config B's widths: 64^2 cfgB64 U-Net (synthetic weights), "
+                   f"B = {a.batch}, {a.steps} steps; ms per step = fastest timed window / steps",
+           "order": f"same device, interleaved uncond_parent, uncond, replace, ps for {a.rounds} rounds; each a "
+                    "child process, one untimed window first",
+           "summary": summary, "runs": res}
+    text = json.dumps(doc, indent=1)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(text + "\n")
+    print(json.dumps(summary))
+
+
+if __name__ == "__main__":
+    main()

@@ -76,6 +76,12 @@ _SIGS = {
                                        C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int64,
                                        C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
                                        C.c_void_p, C.c_uint64, C.c_void_p]),
+    "cfd_sched_step_jump": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int64,
+                                      C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
+                                      C.c_void_p, C.c_uint64, C.c_float, C.c_float, C.c_void_p, C.c_uint64,
+                                      C.c_void_p]),
+    "cfd_sampler_set_jumps": (C.c_int, [C.c_void_p, C.c_void_p]),
     "cfd_sampler_set_known": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
                                         C.c_void_p]),
     "cfd_sampler_captures": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),

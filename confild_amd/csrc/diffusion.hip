@@ -82,7 +82,7 @@ struct StepArgs {
     const SamplerCtl* ctl;         // native loop: (seed, counter, goff) from device memory, or null
 };
 
-// Known-row replacement (step_kernel<true>): after the step's sample s,
+// Known-row replacement (step_kernel<true, *>): after the step's sample s,
 //   q = a_i * known + b_i * n2,  out = m * q + (1 - m) * s
 // with (a_i, b_i) = (sqrt(abar_prev[i]), sqrt(1 - abar_prev[i])) from `tab`.
 struct KnownArgs {
@@ -94,8 +94,21 @@ struct KnownArgs {
     uint64_t counter2;    // read from ctl->counter2 in the native loop
 };
 
-template <bool KNOWN>
-__global__ void step_kernel(StepArgs a, KnownArgs kn) {
+// Resampling jump (step_kernel<true, true>): after the known-row step's out,
+//   out = ja * out + jb * z3
+// the merged forward step from the level the step produced up to level `to`,
+// (ja, jb) = (sqrt(rho), sqrt(1 - rho)), rho = abar[to] / abar[i - 1].  jb == 0
+// (a step of the schedule that does not jump) leaves the known-row step's bits.
+struct JumpArgs {
+    float ja, jb;
+    const float* noise3;  // may be null -> Philox(seed, counter3)
+    uint64_t counter3;    // read from ctl->counter3 in the native loop
+    const float* jtab;    // native loop: (n_steps, 2) rows (ja, jb) indexed by the step number, or null
+    int64_t n_steps;      // rows of jtab
+};
+
+template <bool KNOWN, bool JUMP>
+__global__ void step_kernel(StepArgs a, KnownArgs kn, JumpArgs jp) {
 #pragma clang fp contract(off)
     const int64_t grp = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t base = grp * 4;
@@ -118,6 +131,29 @@ __global__ void step_kernel(StepArgs a, KnownArgs kn) {
             Philox::normal4(a.ctl->seed, a.ctl->counter2, a.ctl->goff + (uint64_t)grp, z2);
         } else {
             Philox::normal4(a.seed, kn.counter2, a.goff + (uint64_t)grp, z2);
+        }
+    }
+    float ja = 1.0f, jb = 0.0f;
+    float z3[4] = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (JUMP) {
+        ja = jp.ja;
+        jb = jp.jb;
+        if (jp.jtab) {
+            // the step number is the same for the whole launch: a uniform load
+            const uint64_t k = a.ctl->counter;
+            CFD_DASSERT(k < (uint64_t)jp.n_steps);
+            ja = jp.jtab[k * 2];
+            jb = jp.jtab[k * 2 + 1];
+        }
+        if (jb != 0.0f) {
+            if (jp.noise3) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) z3[j] = (base + j < a.total) ? jp.noise3[base + j] : 0.f;
+            } else if (a.ctl) {
+                Philox::normal4(a.ctl->seed, a.ctl->counter3, a.ctl->goff + (uint64_t)grp, z3);
+            } else {
+                Philox::normal4(a.seed, jp.counter3, a.goff + (uint64_t)grp, z3);
+            }
         }
     }
 #pragma unroll
@@ -148,6 +184,9 @@ __global__ void step_kernel(StepArgs a, KnownArgs kn) {
             const float m = kn.mask[b * kn.mask_bstride + e];
             const float q = kn.tab[t * 2] * kn.known[b * kn.known_bstride + e] + kn.tab[t * 2 + 1] * z2[j];
             out = m * q + (1.0f - m) * out;
+        }
+        if constexpr (JUMP) {
+            if (jb != 0.0f) out = ja * out + jb * z3[j];
         }
         a.x_out[i] = out;
         if (a.xs_out) a.xs_out[i] = xs;
@@ -323,6 +362,7 @@ __global__ void sampler_advance_kernel(SamplerCtl* ctl, const int64_t* __restric
     if (threadIdx.x == 0) {
         ctl->counter = k;
         ctl->counter2 = CFD_KNOWN_COUNTER + k;
+        ctl->counter3 = CFD_JUMP_COUNTER + k;
         ctl->k = k + 1;
     }
 }
@@ -332,6 +372,7 @@ __global__ void sampler_set_kernel(SamplerCtl* ctl, uint64_t k, uint64_t seed, u
         ctl->k = k;
         ctl->counter = k;
         ctl->counter2 = CFD_KNOWN_COUNTER + k;
+        ctl->counter3 = CFD_JUMP_COUNTER + k;
         ctl->seed = seed;
         ctl->goff = goff;
     }
@@ -364,7 +405,8 @@ void launch_sched_step_ctl(const cfd_sched* s, int kind, int clip, float* x, con
                            const SamplerCtl* ctl, int64_t n_per_sample, int B, hipStream_t st) {
     StepArgs a{s->coefs, x, eps, t, nullptr, x, nullptr, n_per_sample, n_per_sample * B, 0, 0, 0, kind, clip, ctl};
     const int64_t groups = ceil_div(a.total, 4);
-    hipLaunchKernelGGL(step_kernel<false>, dim3((unsigned)ceil_div(groups, 256)), dim3(256), 0, st, a, KnownArgs{});
+    hipLaunchKernelGGL((step_kernel<false, false>), dim3((unsigned)ceil_div(groups, 256)), dim3(256), 0, st, a, KnownArgs{},
+                       JumpArgs{});
     check_launch("step_kernel");
 }
 
@@ -374,8 +416,20 @@ void launch_sched_step_known_ctl(const cfd_sched* s, int kind, int clip, float* 
     StepArgs a{s->coefs, x, eps, t, nullptr, x, nullptr, n_per_sample, n_per_sample * B, 0, 0, 0, kind, clip, ctl};
     KnownArgs kn{known, mask, n_per_sample, n_per_sample, table, nullptr, 0};
     const int64_t groups = ceil_div(a.total, 4);
-    hipLaunchKernelGGL(step_kernel<true>, dim3((unsigned)ceil_div(groups, 256)), dim3(256), 0, st, a, kn);
+    hipLaunchKernelGGL((step_kernel<true, false>), dim3((unsigned)ceil_div(groups, 256)), dim3(256), 0, st, a, kn,
+                       JumpArgs{});
     check_launch("step_kernel<known>");
+}
+
+void launch_sched_step_jump_ctl(const cfd_sched* s, int kind, int clip, float* x, const float* eps, const int64_t* t,
+                                const SamplerCtl* ctl, const float* known, const float* mask, const float* table,
+                                const float* jtab, int n_steps, int64_t n_per_sample, int B, hipStream_t st) {
+    StepArgs a{s->coefs, x, eps, t, nullptr, x, nullptr, n_per_sample, n_per_sample * B, 0, 0, 0, kind, clip, ctl};
+    KnownArgs kn{known, mask, n_per_sample, n_per_sample, table, nullptr, 0};
+    JumpArgs jp{1.0f, 0.0f, nullptr, 0, jtab, n_steps};
+    const int64_t groups = ceil_div(a.total, 4);
+    hipLaunchKernelGGL((step_kernel<true, true>), dim3((unsigned)ceil_div(groups, 256)), dim3(256), 0, st, a, kn, jp);
+    check_launch("step_kernel<known, jump>");
 }
 }  // namespace cfd
 
@@ -409,8 +463,8 @@ extern "C" int cfd_sched_step(const cfd_sched* s, int kind, int clip, const floa
         cfd::StepArgs a{s->coefs, x, eps, t, noise, x_out, xstart_out, n_per_sample, n_per_sample * B,
                         seed, counter, offset / 4, kind, clip, nullptr};
         const int64_t groups = cfd::ceil_div(a.total, 4);
-        hipLaunchKernelGGL(cfd::step_kernel<false>, dim3((unsigned)cfd::ceil_div(groups, 256)), dim3(256), 0,
-                           (hipStream_t)stream, a, cfd::KnownArgs{});
+        hipLaunchKernelGGL((cfd::step_kernel<false, false>), dim3((unsigned)cfd::ceil_div(groups, 256)), dim3(256), 0,
+                           (hipStream_t)stream, a, cfd::KnownArgs{}, cfd::JumpArgs{});
         cfd::check_launch("step_kernel");
     });
 }
@@ -433,9 +487,34 @@ extern "C" int cfd_sched_step_known(const cfd_sched* s, int kind, int clip, cons
                         seed, counter, offset / 4, kind, clip, nullptr};
         cfd::KnownArgs kn{known, mask, known_bstride, mask_bstride, table, noise2, counter2};
         const int64_t groups = cfd::ceil_div(a.total, 4);
-        hipLaunchKernelGGL(cfd::step_kernel<true>, dim3((unsigned)cfd::ceil_div(groups, 256)), dim3(256), 0,
-                           (hipStream_t)stream, a, kn);
+        hipLaunchKernelGGL((cfd::step_kernel<true, false>), dim3((unsigned)cfd::ceil_div(groups, 256)), dim3(256), 0,
+                           (hipStream_t)stream, a, kn, cfd::JumpArgs{});
         cfd::check_launch("step_kernel<known>");
+    });
+}
+
+extern "C" int cfd_sched_step_jump(const cfd_sched* s, int kind, int clip, const float* x, const float* eps,
+                                   const int64_t* t, const float* noise, uint64_t seed, uint64_t counter,
+                                   uint64_t offset, float* x_out, float* xstart_out, int64_t n_per_sample, int B,
+                                   const float* known, int64_t known_bstride, const float* mask,
+                                   int64_t mask_bstride, const float* table, const float* noise2, uint64_t counter2,
+                                   float ja, float jb, const float* noise3, uint64_t counter3, void* stream) {
+    return cfd::guard([&] {
+        CFD_REQUIRE(s && x && eps && t && x_out && known && mask && table, CFD_EARG, "null argument");
+        CFD_REQUIRE(offset % 4 == 0, CFD_EARG, "noise offset must be a multiple of 4");
+        CFD_REQUIRE(kind == CFD_STEP_DDPM || kind == CFD_STEP_DDIM, CFD_EARG, "unknown step kind");
+        CFD_REQUIRE(n_per_sample > 0 && B > 0, CFD_EARG, "empty step");
+        CFD_REQUIRE((known_bstride == 0 || known_bstride == n_per_sample) &&
+                        (mask_bstride == 0 || mask_bstride == n_per_sample),
+                    CFD_EARG, "known rows and mask must be shared (stride 0) or per sample (stride n)");
+        cfd::StepArgs a{s->coefs, x, eps, t, noise, x_out, xstart_out, n_per_sample, n_per_sample * B,
+                        seed, counter, offset / 4, kind, clip, nullptr};
+        cfd::KnownArgs kn{known, mask, known_bstride, mask_bstride, table, noise2, counter2};
+        cfd::JumpArgs jp{ja, jb, noise3, counter3, nullptr, 0};
+        const int64_t groups = cfd::ceil_div(a.total, 4);
+        hipLaunchKernelGGL((cfd::step_kernel<true, true>), dim3((unsigned)cfd::ceil_div(groups, 256)), dim3(256), 0,
+                           (hipStream_t)stream, a, kn, jp);
+        cfd::check_launch("step_kernel<known, jump>");
     });
 }
 

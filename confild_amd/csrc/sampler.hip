@@ -44,13 +44,19 @@ struct cfd_sampler {
     float* ktab = nullptr;          // (n_t, 2)
     int has_known = 0;
     hipGraphExec_t kexec[2] = {nullptr, nullptr};
+    // resampling jumps (cfd_sampler_set_jumps): per step of the loop (ja, jb), (1, 0)
+    // where it does not jump; the jump step (known rows, then the jump) has a third
+    // pair of graphs
+    float* jtab = nullptr;          // (n_steps, 2)
+    int has_jumps = 0;
+    hipGraphExec_t jexec[2] = {nullptr, nullptr};
     uint64_t captures = 0;          // graph captures so far (cfd_sampler_captures)
 };
 
 namespace {
 
 void destroy_graphs(cfd_sampler* sp) {
-    for (auto* set : {sp->exec, sp->kexec})
+    for (auto* set : {sp->exec, sp->kexec, sp->jexec})
         for (int i = 0; i < 2; ++i)
             if (set[i]) {
                 (void)hipGraphExecDestroy(set[i]);
@@ -59,11 +65,17 @@ void destroy_graphs(cfd_sampler* sp) {
     sp->exec_version = ~uint64_t(0);
 }
 
+// which epilogue a step runs, and which pair of graphs holds it
+enum StepMode { STEP_PLAIN = 0, STEP_KNOWN = 1, STEP_JUMP = 2 };
+
 // one reverse step on `st`: advance the timesteps, eps = U-Net(x, t), x = step(x, eps)
-void enqueue_step(const cfd_sampler* sp, bool known, hipStream_t st) {
+void enqueue_step(const cfd_sampler* sp, StepMode mode, hipStream_t st) {
     cfd::launch_sampler_advance(sp->ctl, sp->tseq, sp->tseq + sp->n_steps, sp->tbuf, sp->tbuf + sp->B, sp->B, st);
     cfd::unet_forward_raw(sp->unet, sp->x, sp->tbuf + sp->B, sp->eps, sp->B, sp->ws, st);
-    if (known)
+    if (mode == STEP_JUMP)
+        cfd::launch_sched_step_jump_ctl(sp->sched, sp->kind, sp->clip, sp->x, sp->eps, sp->tbuf, sp->ctl, sp->known,
+                                        sp->kmask, sp->ktab, sp->jtab, sp->n_steps, sp->n_per_sample, sp->B, st);
+    else if (mode == STEP_KNOWN)
         cfd::launch_sched_step_known_ctl(sp->sched, sp->kind, sp->clip, sp->x, sp->eps, sp->tbuf, sp->ctl, sp->known,
                                          sp->kmask, sp->ktab, sp->n_per_sample, sp->B, st);
     else
@@ -71,7 +83,7 @@ void enqueue_step(const cfd_sampler* sp, bool known, hipStream_t st) {
                                    sp->n_per_sample, sp->B, st);
 }
 
-hipGraphExec_t capture(cfd_sampler* sp, bool known, int steps) {
+hipGraphExec_t capture(cfd_sampler* sp, StepMode mode, int steps) {
     ++sp->captures;
     hipStream_t cs;
     CFD_HIP(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
@@ -80,7 +92,7 @@ hipGraphExec_t capture(cfd_sampler* sp, bool known, int steps) {
     try {
         CFD_HIP(hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal));
         try {
-            for (int i = 0; i < steps; ++i) enqueue_step(sp, known, cs);
+            for (int i = 0; i < steps; ++i) enqueue_step(sp, mode, cs);
         } catch (...) {
             hipGraph_t dummy = nullptr;
             (void)hipStreamEndCapture(cs, &dummy);
@@ -155,6 +167,7 @@ extern "C" void cfd_sampler_destroy(cfd_sampler* sp) {
     (void)hipFree(sp->known);
     (void)hipFree(sp->kmask);
     (void)hipFree(sp->ktab);
+    (void)hipFree(sp->jtab);
     delete sp;
 }
 
@@ -164,6 +177,8 @@ extern "C" int cfd_sampler_run(cfd_sampler* sp, const float* x_in, float* x_out,
         CFD_REQUIRE(sp, CFD_EARG, "null sampler");
         CFD_REQUIRE(0 <= k0 && k0 <= k1 && k1 <= sp->n_steps, CFD_EARG, "step range outside the loop");
         CFD_REQUIRE(offset % 4 == 0, CFD_EARG, "noise offset must be a multiple of 4");
+        CFD_REQUIRE(!sp->has_jumps || sp->has_known, CFD_EARG,
+                    "resampling jumps need known rows (cfd_sampler_set_known)");
         cfd::unet_check_ready(sp->unet);
         cfd::DeviceGuard dg(sp->device);
         const hipStream_t st = (hipStream_t)stream;
@@ -182,22 +197,22 @@ extern "C" int cfd_sampler_run(cfd_sampler* sp, const float* x_in, float* x_out,
         if (x_in) CFD_HIP(hipMemcpyAsync(sp->x, x_in, bytes, hipMemcpyDeviceToDevice, st));
         cfd::launch_sampler_set(sp->ctl, (uint64_t)k0, seed, offset / 4, st);
         int k = k0;
-        const bool known = sp->has_known != 0;
+        const StepMode mode = sp->has_jumps ? STEP_JUMP : sp->has_known ? STEP_KNOWN : STEP_PLAIN;
         if (sp->graph) {
             if (sp->exec_version != cfd::unet_version(sp->unet)) {
                 destroy_graphs(sp);
                 sp->exec_version = cfd::unet_version(sp->unet);
             }
-            hipGraphExec_t* ex = known ? sp->kexec : sp->exec;
+            hipGraphExec_t* ex = mode == STEP_JUMP ? sp->jexec : mode == STEP_KNOWN ? sp->kexec : sp->exec;
             if (!ex[0]) {
-                // the plain and the conditioned step are captured when first run
-                ex[0] = capture(sp, known, 1);
-                if (sp->unroll > 1) ex[1] = capture(sp, known, sp->unroll);
+                // the plain, the conditioned and the jump step are captured when first run
+                ex[0] = capture(sp, mode, 1);
+                if (sp->unroll > 1) ex[1] = capture(sp, mode, sp->unroll);
             }
             for (; sp->unroll > 1 && k + sp->unroll <= k1; k += sp->unroll) CFD_HIP(hipGraphLaunch(ex[1], st));
             for (; k < k1; ++k) CFD_HIP(hipGraphLaunch(ex[0], st));
         } else {
-            for (; k < k1; ++k) enqueue_step(sp, known, st);
+            for (; k < k1; ++k) enqueue_step(sp, mode, st);
         }
         if (x_out) CFD_HIP(hipMemcpyAsync(x_out, sp->x, bytes, hipMemcpyDeviceToDevice, st));
     });
@@ -229,6 +244,29 @@ extern "C" int cfd_sampler_set_known(cfd_sampler* sp, const float* known, int64_
         }
         CFD_HIP(hipMemcpyAsync(sp->ktab, table, tab, hipMemcpyDeviceToDevice, st));
         sp->has_known = 1;
+    });
+}
+
+extern "C" int cfd_sampler_set_jumps(cfd_sampler* sp, const float* host_jtab) {
+    return cfd::guard([&] {
+        CFD_REQUIRE(sp, CFD_EARG, "null sampler");
+        if (!host_jtab) {
+            sp->has_jumps = 0;   // the table and the jump graphs stay for the next set
+            return;
+        }
+        for (int k = 0; k < sp->n_steps; ++k) {
+            const float ja = host_jtab[2 * k], jb = host_jtab[2 * k + 1];
+            CFD_REQUIRE(ja >= 0.0f && ja <= 1.0f && jb >= 0.0f && jb <= 1.0f, CFD_EARG,
+                        "jump coefficients outside [0, 1]");
+        }
+        CFD_REQUIRE(host_jtab[2 * (sp->n_steps - 1) + 1] == 0.0f, CFD_EARG, "the last step cannot jump");
+        cfd::DeviceGuard dg(sp->device);
+        const size_t bytes = sizeof(float) * 2 * (size_t)sp->n_steps;
+        if (!sp->jtab) CFD_HIP(hipMalloc(&sp->jtab, bytes));
+        // a run in flight still reads the table it was given
+        CFD_HIP(hipDeviceSynchronize());
+        CFD_HIP(hipMemcpy(sp->jtab, host_jtab, bytes, hipMemcpyHostToDevice));
+        sp->has_jumps = 1;
     });
 }
 

@@ -13,6 +13,14 @@ state the step produces (cfd_sched_step_known); at the last step the masked
 entries are ``known`` itself.  n2 is Philox (seed, (1 << 41) + k), or
 ``known_noise`` (one tensor per step) in the Python loop.
 
+Resampling: with known rows every loop takes ``resample=(jump_length, jump_n_sample)``
+(RePaint, Lugmayr et al. 2022): the loop walks ``resample_schedule`` and, where a
+step jumps, the same launch also noises the whole state forward by jump_length
+levels, x' = a x + b n3 (``jump_coefs``; cfd_sched_step_jump), so free and known
+rows are re-denoised together jump_n_sample times.  n3 is Philox
+(seed, (1 << 42) + k); k counts executed steps, so a revisited level draws afresh
+(``step_noise`` / ``known_noise`` then hold one tensor per executed step).
+
 RNG: by default the per-step normals come from the in-kernel Philox stream keyed
 by a seed drawn from torch's default CPU generator at loop start (so
 ``torch.manual_seed`` makes runs reproducible).  For parity with a reference run,
@@ -99,6 +107,58 @@ def fresh_seed(noise, seed):
 
 # Philox counter of the known-row noise of step k: KNOWN_COUNTER + k (csrc/sampler.hpp)
 KNOWN_COUNTER = 1 << 41
+# Philox counter of the jump noise after step k: JUMP_COUNTER + k
+JUMP_COUNTER = 1 << 42
+
+
+def resample_schedule(n, jump_length, jump_n_sample):
+    """RePaint's resampling schedule (Lugmayr et al. 2022) over ``n`` table indices as
+    a list of (i, to): entry k is reverse step k of the loop and runs table index i;
+    where ``to`` is not None the state it produced (level i - 1) is then noised
+    forward to level ``to`` = i - 1 + jump_length.  (The state is at level L when the
+    next reverse step is table index L; level -1 is the clean sample.)  Every level
+    t in range(0, n - jump_length, jump_length) is left upwards jump_n_sample - 1
+    times, so n + len(that range) * (jump_n_sample - 1) * jump_length steps in all;
+    jump_n_sample == 1 or jump_length >= n is the plain sequence n - 1 .. 0."""
+    n, J, r = int(n), int(jump_length), int(jump_n_sample)
+    if J < 1:
+        raise ValueError(f"jump_length must be >= 1, got {jump_length}")
+    if r < 1:
+        raise ValueError(f"jump_n_sample must be >= 1, got {jump_n_sample}")
+    left = {t: r - 1 for t in range(0, n - J, J)}
+    out = []
+    L = n - 1
+    while L >= 0:
+        i, L = L, L - 1
+        to = None
+        if left.get(L, 0) > 0:
+            left[L] -= 1
+            to = L + J
+        out.append((i, to))
+        if to is not None:
+            L = to
+    return out
+
+
+def check_resample(resample, has_known, n):
+    """``resample`` as (jump_length, jump_n_sample), or None where the schedule is the
+    plain sequence (jump_n_sample == 1, jump_length >= n); ValueError for a malformed
+    tuple and for jumps without known rows."""
+    if resample is None:
+        return None
+    try:
+        J, r = resample
+        ok = int(J) == J and int(r) == r and not isinstance(J, bool) and not isinstance(r, bool)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"resample must be (jump_length, jump_n_sample), two integers; got {resample!r}")
+    J, r = int(J), int(r)
+    if J < 1 or r < 1:
+        raise ValueError(f"resample needs jump_length >= 1 and jump_n_sample >= 1, got {resample!r}")
+    if not has_known:
+        raise ValueError("resample without known rows (known=, known_mask=)")
+    return None if r == 1 or J >= n else (J, r)
 
 
 def broadcast_rows(v, B, tail, device, what):
@@ -165,6 +225,7 @@ class _NativeLoop:
         self.model, self.sched = model, sched
         ti = np.ascontiguousarray(tidx, dtype=np.int64)
         tm = np.ascontiguousarray(tmodel, dtype=np.int64)
+        self.n_steps = len(ti)
         self.handle = C.c_void_p()
         _lib.check(lib.cfd_sampler_create(handle, sched.handle, kind, 1 if clip else 0, B, n_per_sample, len(ti),
                                           ti.ctypes.data_as(C.c_void_p), tm.ctypes.data_as(C.c_void_p),
@@ -180,6 +241,17 @@ class _NativeLoop:
         _lib.check(lib.cfd_sampler_set_known(self.handle, _lib.ptr(kn.known), kn.kstride, _lib.ptr(kn.mask),
                                              kn.mstride, _lib.ptr(table), _lib.stream_of(device)),
                    "cfd_sampler_set_known")
+
+    def set_jumps(self, jtab):
+        """Resampling jumps: the host (n_steps, 2) fp32 rows (ja, jb) of every step; None clears them."""
+        lib = _lib.load()
+        if jtab is None:
+            _lib.check(lib.cfd_sampler_set_jumps(self.handle, None), "cfd_sampler_set_jumps")
+            return
+        jt = np.ascontiguousarray(jtab, dtype=np.float32)
+        if jt.shape != (self.n_steps, 2):
+            raise ValueError(f"jump table of shape {jt.shape} for a loop of {self.n_steps} steps")
+        _lib.check(lib.cfd_sampler_set_jumps(self.handle, jt.ctypes.data_as(C.c_void_p)), "cfd_sampler_set_jumps")
 
     def captures(self):
         """Graph captures this loop has made so far."""
@@ -236,6 +308,7 @@ class GaussianDiffusion:
         self._scheds = {}
         self._natives = {}
         self._ktabs = {}
+        self._resamples = {}
 
     def _model_timesteps_host(self, indices):
         """Model timesteps of table indices (identity; SpacedDiffusion: timestep_map)."""
@@ -280,6 +353,28 @@ class GaussianDiffusion:
         return torch.stack([f(np.sqrt(self.alphas_cumprod_prev)), f(np.sqrt(1.0 - self.alphas_cumprod_prev))],
                            dim=1).contiguous()
 
+    def jump_coefs(self, i, to):
+        """(a, b) as fp32 of the jump after the step at table index ``i`` up to level
+        ``to``: the forward process from level L = i - 1 to ``to`` in one merged step,
+        rho = abar[to] / abar[L] in float64, a = sqrt(rho), b = sqrt(1 - rho) -- the
+        distribution of to - L single steps sqrt(1 - beta) x + sqrt(beta) eps."""
+        i, to = int(i), int(to)
+        if not 1 <= i <= to < self.num_timesteps:
+            raise ValueError(f"a jump needs 1 <= i <= to <= {self.num_timesteps - 1}, got i {i}, to {to}")
+        rho = self.alphas_cumprod[to] / self.alphas_cumprod[i - 1]
+        return float(np.float32(np.sqrt(rho))), float(np.float32(np.sqrt(1.0 - rho)))
+
+    def _resampled(self, resample):
+        """(schedule, jtab) of a checked ``resample``: the (i, to) list and its (n_rev, 2)
+        fp32 rows (ja, jb), (1, 0) where a step does not jump."""
+        got = self._resamples.get(resample)
+        if got is None:
+            sched = resample_schedule(self.num_timesteps, *resample)
+            jtab = np.array([(1.0, 0.0) if to is None else self.jump_coefs(i, to) for i, to in sched],
+                            dtype=np.float32)
+            got = self._resamples[resample] = (sched, jtab)
+        return got
+
     def _ktab(self, device: torch.device):
         dev = device.index if device.index is not None else torch.cuda.current_device()
         t = self._ktabs.get(dev)
@@ -303,7 +398,8 @@ class GaussianDiffusion:
             raise NotImplementedError(f"model_mean_type {self.model_mean_type} on the HIP path (CoNFiLD uses EPSILON)")
 
     def _step(self, kind, model, x, t, clip_denoised, denoised_fn, cond_fn, model_kwargs, noise, seed, counter, eta,
-              offset=0, kn=None, known_noise=None):
+              offset=0, kn=None, known_noise=None, jump=None):
+        """``jump``: None, or (ja, jb, jump_noise | None) of a resampling jump after the step."""
         self._check_mean_type()
         if denoised_fn is not None or cond_fn is not None:
             raise NotImplementedError("denoised_fn / cond_fn (use the DPS sampler for conditioning)")
@@ -328,6 +424,19 @@ class GaussianDiffusion:
                 nz2 = known_noise.to(device=x.device, dtype=torch.float32).contiguous()
                 if nz2.shape != x.shape:
                     raise ValueError("known_noise must have the shape of x")
+            if jump is not None:
+                ja, jb, nz3 = jump
+                if nz3 is not None:
+                    nz3 = nz3.to(device=x.device, dtype=torch.float32).contiguous()
+                    if nz3.shape != x.shape:
+                        raise ValueError("jump_noise must have the shape of x")
+                _lib.check(_lib.load().cfd_sched_step_jump(
+                    sched.handle, kind, 1 if clip_denoised else 0, _lib.ptr(x), _lib.ptr(eps), _lib.ptr(t),
+                    _lib.ptr(nz), seed, counter, offset, _lib.ptr(out), _lib.ptr(xs), n, x.shape[0],
+                    _lib.ptr(kn.known), kn.kstride, _lib.ptr(kn.mask), kn.mstride, _lib.ptr(self._ktab(x.device)),
+                    _lib.ptr(nz2), KNOWN_COUNTER + counter, ja, jb, _lib.ptr(nz3), JUMP_COUNTER + counter,
+                    _lib.stream_of(x.device)), "cfd_sched_step_jump")
+                return {"sample": out, "pred_xstart": xs}
             _lib.check(_lib.load().cfd_sched_step_known(
                 sched.handle, kind, 1 if clip_denoised else 0, _lib.ptr(x), _lib.ptr(eps), _lib.ptr(t), _lib.ptr(nz),
                 seed, counter, offset, _lib.ptr(out), _lib.ptr(xs), n, x.shape[0], _lib.ptr(kn.known), kn.kstride,
@@ -341,30 +450,52 @@ class GaussianDiffusion:
         return {"sample": out, "pred_xstart": xs}
 
     def p_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None,
-                 noise=None, seed=None, counter=0, known=None, known_mask=None, known_noise=None):
+                 noise=None, seed=None, counter=0, known=None, known_mask=None, known_noise=None, jump_to=None,
+                 jump_noise=None):
         """gaussian_diffusion.py:395-439 (noise: explicit normals, else Philox(seed, counter);
         with neither, a fresh seed per call from torch's generator, like the
-        reference's fresh ``randn_like`` at :430)."""
+        reference's fresh ``randn_like`` at :430).  ``jump_to``: after the step (known
+        rows required, one table index t >= 1 for the whole batch) the state is noised
+        forward to level jump_to, with ``jump_noise`` or Philox(seed, (1 << 42) + counter)."""
         seed = fresh_seed(noise, seed)
         t = t.to(device=x.device, dtype=torch.int64).contiguous()
         kn = _Known.of(known, known_mask, known_noise, x.shape, x.device)
+        jump = self._single_jump(t, kn, jump_to, jump_noise)
         with torch.no_grad():
             return self._step(STEP_DDPM, model, x, t, clip_denoised, denoised_fn, cond_fn, model_kwargs, noise,
-                              seed, counter, 0.0, kn=kn, known_noise=known_noise)
+                              seed, counter, 0.0, kn=kn, known_noise=known_noise, jump=jump)
 
     def ddim_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None,
-                    eta=0.0, noise=None, seed=None, counter=0, known=None, known_mask=None, known_noise=None):
-        """gaussian_diffusion.py:537-585 (noise / seed as p_sample)."""
+                    eta=0.0, noise=None, seed=None, counter=0, known=None, known_mask=None, known_noise=None,
+                    jump_to=None, jump_noise=None):
+        """gaussian_diffusion.py:537-585 (noise / seed / jump_to as p_sample)."""
         seed = fresh_seed(noise, seed)
         t = t.to(device=x.device, dtype=torch.int64).contiguous()
         kn = _Known.of(known, known_mask, known_noise, x.shape, x.device)
+        jump = self._single_jump(t, kn, jump_to, jump_noise)
         with torch.no_grad():
             return self._step(STEP_DDIM, model, x, t, clip_denoised, denoised_fn, cond_fn, model_kwargs, noise,
-                              seed, counter, eta, kn=kn, known_noise=known_noise)
+                              seed, counter, eta, kn=kn, known_noise=known_noise, jump=jump)
+
+    def _single_jump(self, t, kn, jump_to, jump_noise):
+        """The ``jump`` of _step for a single step's (jump_to, jump_noise), or None."""
+        if jump_to is None:
+            if jump_noise is not None:
+                raise ValueError("jump_noise without jump_to")
+            return None
+        if kn is None:
+            raise ValueError("jump_to without known rows (known=, known_mask=)")
+        lo, hi = int(t.min().item()), int(t.max().item())
+        if lo != hi:
+            raise ValueError("jump_to needs one table index for the whole batch")
+        if lo < 1:
+            raise ValueError("jump_to at t = 0: the clean sample is not resampled")
+        return self.jump_coefs(lo, jump_to) + (jump_noise,)
 
     # -- loops ------------------------------------------------------------------
     def _loop(self, kind, model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, device,
-              progress, eta, step_noise, seed, sample_offset=0, known=None, known_mask=None, known_noise=None):
+              progress, eta, step_noise, seed, sample_offset=0, known=None, known_mask=None, known_noise=None,
+              resample=None):
         if device is None:
             try:
                 device = next(model.parameters()).device
@@ -376,6 +507,7 @@ class GaussianDiffusion:
         assert isinstance(shape, (tuple, list))
         lib = _lib.lib()
         kn = _Known.of(known, known_mask, known_noise, shape, device)
+        resample = check_resample(resample, kn is not None, self.num_timesteps)
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
         per_sample = int(np.prod(shape[1:]))
@@ -388,21 +520,26 @@ class GaussianDiffusion:
             img = torch.empty(*shape, dtype=torch.float32, device=device)
             _lib.check(lib.cfd_randn(_lib.ptr(img), img.numel(), seed, 1 << 40, offset, _lib.stream_of(device)),
                        "cfd_randn")
-        indices = list(range(self.num_timesteps))[::-1]
+        if resample is None:
+            indices = [(i, None) for i in range(self.num_timesteps)][::-1]
+        else:
+            indices = self._resampled(resample)[0]   # step k runs table index i, then jumps to level `to`
+        n_rev = len(indices)
         if progress:
             from tqdm.auto import tqdm
             indices = tqdm(indices)
         B = shape[0]
         ts = torch.arange(self.num_timesteps, dtype=torch.int64, device=device)
         self._clear_range_flag(model, device)
-        for k, i in enumerate(indices):
+        for k, (i, to) in enumerate(indices):
             t = ts[i:i + 1].expand(B).contiguous()
             nz = None if step_noise is None else step_noise[k]
             nz2 = None if known_noise is None else known_noise[k]
+            jump = None if to is None else self.jump_coefs(i, to) + (None,)
             with torch.no_grad():
                 out = self._step(kind, model, img, t, clip_denoised, denoised_fn, cond_fn, model_kwargs, nz,
-                                 seed, k, eta, offset, kn=kn, known_noise=nz2)
-            if (k + 1) % RANGE_CHECK_EVERY == 0 or k == len(indices) - 1:
+                                 seed, k, eta, offset, kn=kn, known_noise=nz2, jump=jump)
+            if (k + 1) % RANGE_CHECK_EVERY == 0 or k == n_rev - 1:
                 check_model_range(model, device)   # every RANGE_CHECK_EVERY steps: one stream sync
             yield out
             img = out["sample"]
@@ -421,7 +558,7 @@ class GaussianDiffusion:
                 and not self.rescale_timesteps)
 
     def _native_loop(self, kind, model, shape, noise, clip_denoised, device, eta, seed, sample_offset, known=None,
-                     known_mask=None):
+                     known_mask=None, resample=None):
         """The whole reverse loop on the device (csrc/sampler.hip): bit-identical to
         _loop with Philox noise, without per-step host work."""
         self._check_mean_type()
@@ -441,6 +578,7 @@ class GaussianDiffusion:
         if tuple(shape[1:]) != (model.in_channels, model.image_size, model.image_size):
             raise ValueError(f"shape {tuple(shape)} does not match the model's input")
         kn = _Known.of(known, known_mask, None, shape, device)
+        resample = check_resample(resample, kn is not None, self.num_timesteps)
         if noise is not None:
             img = noise.to(device=device, dtype=torch.float32).contiguous()
         else:
@@ -450,21 +588,29 @@ class GaussianDiffusion:
         h = model._handle(device)   # uploads changed parameters, sets the compute mode
         sched = self._sched(device, eta)
         dev = device.index if device.index is not None else torch.cuda.current_device()
-        key = (id(model), dev, kind, bool(clip_denoised), float(eta), B, NATIVE_MODE, GRAPH_UNROLL)
+        key = (id(model), dev, kind, bool(clip_denoised), float(eta), B, NATIVE_MODE, GRAPH_UNROLL, resample)
         nl = self._natives.get(key)
         if nl is None or nl.model is not model:
             tidx = list(range(self.num_timesteps))[::-1]
+            if resample is not None:
+                # a resampled loop is a loop over the expanded sequence, with its jump table
+                rsched, jtab = self._resampled(resample)
+                tidx = [i for i, _ in rsched]
             with torch.cuda.device(dev):
                 nl = _NativeLoop(model, sched, h, kind, clip_denoised, B, per_sample, tidx,
                                  self._model_timesteps_host(tidx), NATIVE_MODE >= 2, GRAPH_UNROLL)
-            # one loop per (model, device): a new batch size / mode replaces the old one and its buffers
-            self._natives = {k: v for k, v in self._natives.items() if k[:2] != key[:2]}
+                if resample is not None:
+                    nl.set_jumps(jtab)
+            # per (model, device) one plain loop and one resampled loop side by side (a rollout
+            # alternates between them); a new batch size / mode / (J, r) replaces its own kind and its buffers
+            self._natives = {k: v for k, v in self._natives.items()
+                             if k[:2] != key[:2] or (k[-1] is None) != (resample is None)}
             self._natives[key] = nl
         out = torch.empty_like(img)
         self._clear_range_flag(model, device)
         # known rows are copied into the loop's own buffers (or cleared) on every call
         nl.set_known(kn, None if kn is None else self._ktab(device), device)
-        n = self.num_timesteps
+        n = nl.n_steps
         for k0 in range(0, n, RANGE_CHECK_EVERY):
             k1 = min(n, k0 + RANGE_CHECK_EVERY)
             nl.run(img if k0 == 0 else None, out if k1 == n else None, k0, k1, seed, offset, device)
@@ -477,49 +623,53 @@ class GaussianDiffusion:
 
     def p_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
                       model_kwargs=None, device=None, progress=False, step_noise=None, seed=None, sample_offset=0,
-                      known=None, known_mask=None, known_noise=None):
+                      known=None, known_mask=None, known_noise=None, resample=None):
         """gaussian_diffusion.py:441-485.  ``sample_offset``: index of this call's first
         sample in a larger (sharded) batch, so the Philox noise equals the unsharded run's.
         With Philox noise and a HIP UNetModel the loop runs natively (one HIP graph
         per step, csrc/sampler.hip); explicit step_noise / progress use the Python loop."""
         if self._native_ok(model, denoised_fn, cond_fn, model_kwargs, step_noise, progress, known_noise):
             return self._native_loop(STEP_DDPM, model, shape, noise, clip_denoised, device, 0.0, seed, sample_offset,
-                                     known, known_mask)
+                                     known, known_mask, resample)
         final = None
         for s in self.p_sample_loop_progressive(model, shape, noise, clip_denoised, denoised_fn, cond_fn,
                                                 model_kwargs, device, progress, step_noise, seed, sample_offset,
-                                                known, known_mask, known_noise):
+                                                known, known_mask, known_noise, resample):
             final = s
         return final["sample"]
 
     def p_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None,
                                   cond_fn=None, model_kwargs=None, device=None, progress=False, step_noise=None,
-                                  seed=None, sample_offset=0, known=None, known_mask=None, known_noise=None):
-        """gaussian_diffusion.py:487-535."""
+                                  seed=None, sample_offset=0, known=None, known_mask=None, known_noise=None,
+                                  resample=None):
+        """gaussian_diffusion.py:487-535.  With ``resample`` one item per executed step
+        of resample_schedule, after its jump."""
         yield from self._loop(STEP_DDPM, model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs,
-                              device, progress, 0.0, step_noise, seed, sample_offset, known, known_mask, known_noise)
+                              device, progress, 0.0, step_noise, seed, sample_offset, known, known_mask, known_noise,
+                              resample)
 
     def ddim_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
                          model_kwargs=None, device=None, progress=False, eta=0.0, step_noise=None, seed=None,
-                         sample_offset=0, known=None, known_mask=None, known_noise=None):
+                         sample_offset=0, known=None, known_mask=None, known_noise=None, resample=None):
         """gaussian_diffusion.py:625-662 (native loop as p_sample_loop)."""
         if self._native_ok(model, denoised_fn, cond_fn, model_kwargs, step_noise, progress, known_noise):
             return self._native_loop(STEP_DDIM, model, shape, noise, clip_denoised, device, eta, seed, sample_offset,
-                                     known, known_mask)
+                                     known, known_mask, resample)
         final = None
         for s in self.ddim_sample_loop_progressive(model, shape, noise, clip_denoised, denoised_fn, cond_fn,
                                                    model_kwargs, device, progress, eta, step_noise, seed,
-                                                   sample_offset, known, known_mask, known_noise):
+                                                   sample_offset, known, known_mask, known_noise, resample):
             final = s
         return final["sample"]
 
     def ddim_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None,
                                      cond_fn=None, model_kwargs=None, device=None, progress=False, eta=0.0,
                                      step_noise=None, seed=None, sample_offset=0, known=None, known_mask=None,
-                                     known_noise=None):
-        """gaussian_diffusion.py:664-707."""
+                                     known_noise=None, resample=None):
+        """gaussian_diffusion.py:664-707 (resample as p_sample_loop_progressive)."""
         yield from self._loop(STEP_DDIM, model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs,
-                              device, progress, eta, step_noise, seed, sample_offset, known, known_mask, known_noise)
+                              device, progress, eta, step_noise, seed, sample_offset, known, known_mask, known_noise,
+                              resample)
 
     # -- training (the diffusion TrainLoop's loss, U/src/gaussian_diffusion.py:188-206, :744-853) ---------
     def _train_coefs(self, t):

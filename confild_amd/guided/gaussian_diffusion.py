@@ -169,10 +169,13 @@ class _GuidedSampler(SpacedDiffusion):
         self.dense_budget = None  # workspace bytes the dense adjoint may plan for (None: the library default)
 
     def p_sample_loop(self, model, x_start, measurement, measurement_cond_fn, record=False, save_root=None, *,
-                      step_noise=None, seed=None, sample_offset=0, progress=False):
+                      step_noise=None, seed=None, sample_offset=0, progress=False, resample=None):
         """gaussian_diffusion.py:169-206: guided reverse loop from x_start (B, 1, T, L).
         Per-step residual norms (the reference's progress-bar 'distance') are left in
-        ``self.distances`` (steps, B) on the GPU."""
+        ``self.distances`` (steps, B) on the GPU.  ``resample`` is refused: resampling
+        jumps belong to known-row replacement (GaussianDiffusion.p_sample_loop)."""
+        if resample is not None:
+            raise ValueError("resampling jumps are not built for posterior sampling; use known-row replacement")
         if record:
             raise NotImplementedError("record=True (progress images) is not part of the HIP path")
         method, kw = _method_of(measurement_cond_fn)

@@ -21,6 +21,10 @@ reference-preserving defaults:
   rollout_method: replace | ps   (replace: known-row replacement in the native loop;
                                ps: posterior sampling with the 'inpainting' operator)
   rollout_scale: 1.0          (the 'ps' step size)
+  rollout_jump_length: 10     (RePaint resampling in the conditioned 'replace' windows: after every
+  rollout_jump_n_sample: 1     jump_length levels the state is noised back up by jump_length levels
+                               and re-denoised, jump_n_sample times in all, which harmonises free and
+                               known rows at (jump_n_sample - 1) more steps per level.  1: off)
 Known deviation (fixed on purpose): ``channel_mult`` from the YAML IS passed to
 create_model (the reference reads but drops it, inference.py:38-44, so its own
 case4.yml raises ValueError).
@@ -125,9 +129,11 @@ def run(yaml_path: str):
                 raise ValueError("a rollout needs time_length == latent_length == image_size")
             kind = "ddpm" if sampler == "ddpm" else "ddim"     # as the plain run picks its loop
             rdiff, method = rollout_sampler(inp, diff, kind)
+            n_sample = int(getattr(inp, "rollout_jump_n_sample", 1))
+            resample = None if n_sample == 1 else (int(getattr(inp, "rollout_jump_length", 10)), n_sample)
             return extend_latents(model, rdiff, None, windows, int(getattr(inp, "rollout_overlap", T // 2)), method,
                                   scale=float(getattr(inp, "rollout_scale", 1.0)), seed=loop_seed,
-                                  sample_offset=start, sampler=kind, batch_size=count)[:, 0]
+                                  sample_offset=start, sampler=kind, batch_size=count, resample=resample)[:, 0]
         fn = diff.p_sample_loop if sampler == "ddpm" else diff.ddim_sample_loop
         return fn(model, (count, 1, T, L), seed=loop_seed, sample_offset=start)[:, 0]
 

@@ -9,6 +9,9 @@ counterpart for the driver; 'ps' + 'inpainting' is the reference's operator):
   replace  known-row replacement inside the unconditioned loop
            (GaussianDiffusion.p_sample_loop(known=, known_mask=), the native
            graph loop included): one fused elementwise pass per step;
+           ``resample=(jump_length, jump_n_sample)`` adds RePaint's resampling
+           jumps, which re-denoise free and known rows together (more steps
+           per window, the same cost per step);
   ps       posterior sampling with the 'inpainting' operator
            (guided sampler): a U-Net forward and an input VJP per step.
 
@@ -71,18 +74,22 @@ def _ps_method(device, scale):
 
 
 def sample_window(model, diffusion, shape, method, *, known=None, mask=None, scale=1.0, seed, sample_offset=0,
-                  sampler="ddpm", device=None):
+                  sampler="ddpm", device=None, resample=None):
     """One window (B, 1, T, L): unconditioned when ``known`` is None, else conditioned on
     ``known`` where ``mask`` is 1.  ``sampler`` picks the DDPM / DDIM loop for
-    'replace'; a guided sampler ('ps') carries its own kind."""
+    'replace'; a guided sampler ('ps') carries its own kind.  ``resample``
+    (jump_length, jump_n_sample): resampling jumps of a conditioned 'replace' window;
+    an unconditioned window has nothing to harmonise and ignores it."""
     if method not in METHODS:
         raise ValueError(f"method must be one of {METHODS}, got {method!r}")
+    if resample is not None and method != "replace":
+        raise ValueError("resample goes with method 'replace'; posterior sampling ('ps') has no resampling jumps")
     if method == "replace":
         if sampler not in ("ddpm", "ddim"):
             raise ValueError(f"sampler must be 'ddpm' or 'ddim', got {sampler!r}")
         fn = diffusion.p_sample_loop if sampler == "ddpm" else diffusion.ddim_sample_loop
         return fn(model, tuple(shape), device=device, seed=seed, sample_offset=sample_offset, known=known,
-                  known_mask=mask)
+                  known_mask=mask, resample=None if known is None else resample)
     from .guided.gaussian_diffusion import _GuidedSampler
     if not isinstance(diffusion, _GuidedSampler):
         raise TypeError("method 'ps' takes a guided sampler from confild_amd.guided.gaussian_diffusion.create_sampler")
@@ -101,7 +108,7 @@ def sample_window(model, diffusion, shape, method, *, known=None, mask=None, sca
 
 
 def extend_latents(model, diffusion, first, n_windows, overlap, method, *, scale=1.0, seed, sample_offset=0,
-                   sampler="ddpm", batch_size=1):
+                   sampler="ddpm", batch_size=1, resample=None):
     """(B, 1, T + n_windows * (T - overlap), L): ``first`` (B, 1, T, L) continued by
     ``n_windows`` conditioned windows.  ``first=None`` samples window 0 unconditionally:
     ``batch_size`` samples of the model's (1, image_size, image_size) input.
@@ -109,9 +116,12 @@ def extend_latents(model, diffusion, first, n_windows, overlap, method, *, scale
     The stitched sequence keeps the earlier window's values on each overlap and
     appends the later window's rows [overlap, T).  method 'replace' takes a
     GaussianDiffusion, 'ps' a guided sampler (create_sampler) and ``scale``.
-    Window w uses Philox key seed + w."""
+    Window w uses Philox key seed + w.  ``resample`` (jump_length, jump_n_sample):
+    resampling jumps in every conditioned window ('replace' only)."""
     if method not in METHODS:
         raise ValueError(f"method must be one of {METHODS}, got {method!r}")
+    if resample is not None and method != "replace":
+        raise ValueError("resample goes with method 'replace'; posterior sampling ('ps') has no resampling jumps")
     if torch.is_tensor(first):
         if first.dim() != 4 or first.shape[1] != 1:
             raise ValueError(f"first must be (B, 1, T, L), got {tuple(first.shape)}")
@@ -133,6 +143,6 @@ def extend_latents(model, diffusion, first, n_windows, overlap, method, *, scale
     for w in range(1, n_windows + 1):
         known, mask = known_rows(seq[:, :, -T:], overlap)
         win = sample_window(model, diffusion, shape, method, known=known, mask=mask, scale=scale, seed=seed + w,
-                            sample_offset=sample_offset, sampler=sampler, device=device)
+                            sample_offset=sample_offset, sampler=sampler, device=device, resample=resample)
         seq = torch.cat([seq, win[:, :, overlap:]], dim=2)
     return seq

@@ -185,6 +185,24 @@ int  cfd_sched_step_known(const cfd_sched* s, int kind, int clip, const float* x
                           uint64_t offset, float* x_out, float* xstart_out, int64_t n_per_sample, int B,
                           const float* known, int64_t known_bstride, const float* mask, int64_t mask_bstride,
                           const float* table, const float* noise2, uint64_t counter2, void* stream);
+/* cfd_sched_step_known followed by a resampling jump (RePaint, Lugmayr et al. 2022;
+ * no reference counterpart).  With out the known-row step's result, at the noise
+ * level L = i - 1 the step at table index i produces:
+ *   x_out = ja * out + jb * n3          (fp contraction off, in this order)
+ * the forward process from level L to level L + J in one merged step,
+ *   rho = abar[L + J] / abar[L],  (ja, jb) = (sqrt(rho), sqrt(1 - rho)) as fp32
+ * (the distribution of J single steps sqrt(1 - beta) x + sqrt(beta) eps).  jb == 0
+ * skips the jump: x_out is cfd_sched_step_known's, bit for bit.  xstart_out is
+ * unaffected.  n3: noise3 (B*n device normals), or NULL for Philox (seed, counter3)
+ * at stream position offset + element; the loops use counter3 = (1 << 42) + k, a
+ * fourth range beside k, 1 << 40 and (1 << 41) + k.  Same argument checks as
+ * cfd_sched_step_known. */
+int  cfd_sched_step_jump(const cfd_sched* s, int kind, int clip, const float* x, const float* eps,
+                         const int64_t* t, const float* noise, uint64_t seed, uint64_t counter,
+                         uint64_t offset, float* x_out, float* xstart_out, int64_t n_per_sample, int B,
+                         const float* known, int64_t known_bstride, const float* mask, int64_t mask_bstride,
+                         const float* table, const float* noise2, uint64_t counter2, float ja, float jb,
+                         const float* noise3, uint64_t counter3, void* stream);
 /* Native reverse loop (p_sample_loop / ddim_sample_loop, gaussian_diffusion.py:
  * 441-535 / 625-707, with Philox noise): per step the timestep advance, the U-Net
  * forward and the K6 epilogue, with no host work between steps.  graph != 0
@@ -226,6 +244,17 @@ int  cfd_sampler_run(cfd_sampler* sp, const float* x_in, float* x_out, int k0, i
 int  cfd_sampler_set_known(cfd_sampler* sp, const float* known, int64_t known_bstride, const float* mask,
                            int64_t mask_bstride, const float* table, void* stream);
 int  cfd_sampler_captures(const cfd_sampler* sp, uint64_t* n);
+/* Resampling jumps for the following cfd_sampler_run calls.  A resampled loop is a
+ * sampler created with the expanded step sequence (a level is visited more than
+ * once; host_tidx / host_tmodel repeat accordingly); host_jtab is a host array of
+ * n_steps rows (ja, jb), (1, 0) where step k does not jump, copied into a table
+ * the sampler owns.  Every step then becomes cfd_sched_step_jump with (ja, jb)
+ * read from row k and counter3 = (1 << 42) + k, on a third pair of captured graphs:
+ * the whole schedule replays one graph, with no host work at the jump points.
+ * Needs known rows: cfd_sampler_run returns CFD_EARG while jumps are set and
+ * known rows are not.  host_jtab == NULL clears the jumps.  Synchronises the
+ * device (the table is rewritten in place). */
+int  cfd_sampler_set_jumps(cfd_sampler* sp, const float* host_jtab);
 /* n standard normals from Philox4x32-10 (seed, counter) at stream positions
  * offset .. offset+n-1 (offset % 4 == 0): the device-side stand-in for th.randn
  * (gaussian_diffusion.py:513). */

@@ -5,14 +5,18 @@
   replace                 the loop with known-row replacement (cfd_sched_step_known in the graph)
   ps                      posterior sampling with the 'inpainting' operator (Python loop:
                           U-Net forward with tape, cfd_dps_latent_residual, input VJP, update)
+  resample                replace with RePaint resampling jumps, resample=(10, 10)
+                          (cfd_sched_step_jump in the graph; 2,506 executed steps for 256 levels)
 
     python tools/rollout_bench.py [--parent libconfild_hip_parent.so] [--rounds 3] [--out profiles/rollout.json]
 
-Each timing is a child process (CFD_LIB selects the in-tree build), the four run
+Each timing is a child process (CFD_LIB selects the in-tree build), the five run
 interleaved for ``--rounds`` rounds on the same device.  A child builds the
 synthetic cfgB64 U-Net, runs one whole window untimed (graph capture, first
 launches), then times ``--loops`` windows with a host clock around work that ends
-in a device synchronise.  The parent library lacks this change's symbols
+in a device synchronise.  ms per step divides by the steps the loop executes
+(``steps_run``; the resampled window runs more of them than it has levels).  The
+parent library lacks this change's symbols
 (_lib.load binds what a CFD_LIB build exports); its child leaves the known rows out.
 """
 from __future__ import annotations
@@ -24,12 +28,14 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+RESAMPLE = (10, 10)   # (jump_length, jump_n_sample) of the `resample` mode
 
 CHILD = r"""
 import ast, json, sys, time
 import numpy as np, torch
 sys.path.insert(0, sys.argv[1])
 mode, loops, steps, B = sys.argv[2], int(sys.argv[3]), sys.argv[4], int(sys.argv[5])
+resample = ast.literal_eval(sys.argv[6])
 from confild_amd import _lib, synth
 from confild_amd import gaussian_diffusion as gd
 if mode == "uncond_parent":
@@ -56,7 +62,9 @@ if mode == "ps":
     run = lambda: rollout.sample_window(m, d, shape, "ps", known=known, mask=mask, scale=0.5, seed=3)
 else:
     d = create_gaussian_diffusion(steps=1000, noise_schedule="cosine", timestep_respacing=steps)
-    kwargs = dict(known=known, known_mask=mask) if mode == "replace" else {}
+    kwargs = dict(known=known, known_mask=mask) if mode in ("replace", "resample") else {}
+    if mode == "resample":
+        kwargs["resample"] = resample
     run = lambda: d.p_sample_loop(m, shape, seed=3, **kwargs)
 out = run()
 torch.cuda.synchronize()
@@ -68,18 +76,19 @@ for _ in range(loops):
     torch.cuda.synchronize()
     ts.append(time.perf_counter() - t0)
 n = d.num_timesteps
-print(json.dumps({"mode": mode, "lib": _lib.LIB_PATH.rsplit("/", 1)[-1], "steps": n, "B": B,
-                  "window_ms": [1e3 * t for t in ts], "ms_per_step": 1e3 * min(ts) / n}))
+n_run = len(gd.resample_schedule(n, *resample)) if mode == "resample" else n
+print(json.dumps({"mode": mode, "lib": _lib.LIB_PATH.rsplit("/", 1)[-1], "steps": n, "steps_run": n_run, "B": B,
+                  "window_ms": [1e3 * t for t in ts], "ms_per_step": 1e3 * min(ts) / n_run}))
 """
 
 
-def child(mode, lib, loops, steps, B):
+def child(mode, lib, loops, steps, B, resample):
     env = dict(os.environ)
     if lib:
         env["CFD_LIB"] = lib
     else:
         env.pop("CFD_LIB", None)
-    p = subprocess.run([sys.executable, "-c", CHILD, ROOT, mode, str(loops), steps, str(B)], env=env,
+    p = subprocess.run([sys.executable, "-c", CHILD, ROOT, mode, str(loops), steps, str(B), repr(resample)], env=env,
                        capture_output=True, text=True, timeout=600)
     if p.returncode != 0:
         raise SystemExit(f"{mode} ({lib or 'default library'}) failed with {p.returncode}:\n{p.stderr[-2000:]}")
@@ -96,18 +105,22 @@ def main():
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    runs = [("uncond_parent", a.parent), ("uncond", None), ("replace", None), ("ps", None)]
+    runs = [("uncond_parent", a.parent), ("uncond", None), ("replace", None), ("ps", None), ("resample", None)]
+    resample = RESAMPLE
     res = {mode: [] for mode, _ in runs}
     for r in range(a.rounds):
         for mode, lib in runs:
-            loops = 1 if mode == "ps" else a.loops
-            one = child(mode, lib, loops, a.steps, a.batch)
+            loops = 1 if mode in ("ps", "resample") else a.loops   # the two long windows: one timed each
+            one = child(mode, lib, loops, a.steps, a.batch, resample)
             res[mode].append(one)
-            print(f"round {r} {mode:14s} {one['ms_per_step']:.3f} ms/step", flush=True)
-    summary = {mode: {"ms_per_step": [x["ms_per_step"] for x in v]} for mode, v in res.items()}
+            print(f"round {r} {mode:14s} {one['ms_per_step']:.3f} ms/step, window {min(one['window_ms']):.1f} ms "
+                  f"({one['steps_run']} steps)", flush=True)
+    summary = {mode: {"ms_per_step": [x["ms_per_step"] for x in v], "window_ms": [min(x["window_ms"]) for x in v],
+                      "steps_run": v[0]["steps_run"]} for mode, v in res.items()}
     doc = {"what": "one rollout window at config B's widths: 64^2 cfgB64 U-Net (synthetic weights), "
-                   f"B = {a.batch}, {a.steps} steps; ms per step = fastest timed window / steps",
-           "order": f"same device, interleaved uncond_parent, uncond, replace, ps for {a.rounds} rounds; each a "
+                   f"B = {a.batch}, {a.steps} steps (resample {resample}: steps_run executed steps); "
+                   "ms per step = fastest timed window / steps_run",
+           "order": f"same device, interleaved uncond_parent, uncond, replace, ps, resample for {a.rounds} rounds; each a "
                     "child process, one untimed window first",
            "summary": summary, "runs": res}
     text = json.dumps(doc, indent=1)

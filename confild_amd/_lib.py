@@ -105,6 +105,9 @@ _SIGS = {
                                       C.c_void_p]),
     "cfd_dps_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int64,
                                  C.c_void_p]),
+    "cfd_dps_update_known": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p,
+                                       C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
+                                       C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p]),
     "cfd_siren_create": (C.c_int, [C.POINTER(SirenCfg), C.c_int, C.POINTER(C.c_void_p)]),
     "cfd_siren_destroy": (None, [C.c_void_p]),
     "cfd_siren_num_params": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),

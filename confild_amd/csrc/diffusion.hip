@@ -348,6 +348,82 @@ __global__ void dps_update_kernel(const float* __restrict__ sample, const float*
     x_out[i] = sample[i] - (g_direct[i] + g_unet[i]) * scale;
 }
 
+// cfd_dps_update followed by known-row replacement (the guided sampler with known rows):
+//   img = sample - (g_direct + g_unet) * scale     (dps_update_kernel's expression, the same bits)
+//   q   = a_i * known + b_i * n2,  out = m * q + (1 - m) * img     (step_kernel<true, *>'s, the same bits)
+// Four elements per thread and step_kernel's Philox group offset, so n2 is the
+// normal step_kernel<true, false> draws for the same (seed, counter2, offset).
+struct DpsKnownArgs {
+    const float* sample;
+    const float* g_direct;
+    const float* g_unet;
+    float scale;
+    float* x_out;
+    const int64_t* t;     // (B) table indices
+    int64_t n;            // elements per sample
+    int64_t total;        // B * n
+    uint64_t seed, goff;  // goff: Philox group offset (= element offset / 4)
+    int vec;              // every array 16-byte aligned and n % 4 == 0: a group is one f4 of one sample
+};
+
+__device__ __forceinline__ float dps_known_elem(float s, float gd, float gu, float scale, float a, float b, float kv,
+                                                float m, float z2) {
+#pragma clang fp contract(off)
+    const float img = s - (gd + gu) * scale;
+    const float q = a * kv + b * z2;
+    return m * q + (1.0f - m) * img;
+}
+
+__global__ void dps_update_known_kernel(DpsKnownArgs a, KnownArgs kn) {
+#pragma clang fp contract(off)
+    const int64_t grp = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t base = grp * 4;
+    if (base >= a.total) return;
+    float z2[4];
+    if (kn.noise2) {
+        if (a.vec) {
+            const f4 v = *(const f4*)(kn.noise2 + base);
+            z2[0] = v.x, z2[1] = v.y, z2[2] = v.z, z2[3] = v.w;
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) z2[j] = (base + j < a.total) ? kn.noise2[base + j] : 0.f;
+        }
+    } else {
+        Philox::normal4(a.seed, kn.counter2, a.goff + (uint64_t)grp, z2);
+    }
+    if (a.vec) {
+        // n % 4 == 0: the group's four elements belong to one sample
+        const int64_t b = base / a.n;
+        const int64_t e = base - b * a.n;
+        CFD_DASSERT(base + 3 < a.total && e + 3 < a.n);
+        const int64_t t = a.t[b];
+        const float ta = kn.tab[t * 2], tb = kn.tab[t * 2 + 1];
+        const f4 s = *(const f4*)(a.sample + base);
+        const f4 gd = *(const f4*)(a.g_direct + base);
+        const f4 gu = *(const f4*)(a.g_unet + base);
+        const f4 kv = *(const f4*)(kn.known + b * kn.known_bstride + e);
+        const f4 m = *(const f4*)(kn.mask + b * kn.mask_bstride + e);
+        f4 o;
+        o.x = dps_known_elem(s.x, gd.x, gu.x, a.scale, ta, tb, kv.x, m.x, z2[0]);
+        o.y = dps_known_elem(s.y, gd.y, gu.y, a.scale, ta, tb, kv.y, m.y, z2[1]);
+        o.z = dps_known_elem(s.z, gd.z, gu.z, a.scale, ta, tb, kv.z, m.z, z2[2]);
+        o.w = dps_known_elem(s.w, gd.w, gu.w, a.scale, ta, tb, kv.w, m.w, z2[3]);
+        *(f4*)(a.x_out + base) = o;
+        return;
+    }
+    // unaligned arrays or n % 4 != 0 (a group may straddle samples, the last one may be short)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int64_t i = base + j;
+        if (i >= a.total) break;
+        const int64_t b = i / a.n;
+        const int64_t e = i - b * a.n;
+        const int64_t t = a.t[b];
+        a.x_out[i] = dps_known_elem(a.sample[i], a.g_direct[i], a.g_unet[i], a.scale, kn.tab[t * 2], kn.tab[t * 2 + 1],
+                                    kn.known[b * kn.known_bstride + e], kn.mask[b * kn.mask_bstride + e], z2[j]);
+    }
+}
+
 // native loop bookkeeping (one workgroup): the step's timesteps from the
 // host-built sequences, and the step counter for the Philox stream
 __global__ void sampler_advance_kernel(SamplerCtl* ctl, const int64_t* __restrict__ tidx_seq,
@@ -605,6 +681,31 @@ extern "C" int cfd_dps_update(const float* sample, const float* g_direct, const 
         hipLaunchKernelGGL(cfd::dps_update_kernel, dim3((unsigned)cfd::ceil_div(n, 256)), dim3(256), 0,
                            (hipStream_t)stream, sample, g_direct, g_unet, scale, x_out, n);
         cfd::check_launch("dps_update_kernel");
+    });
+}
+
+extern "C" int cfd_dps_update_known(const float* sample, const float* g_direct, const float* g_unet, float scale,
+                                    float* x_out, const int64_t* t, int64_t n_per_sample, int B, const float* known,
+                                    int64_t known_bstride, const float* mask, int64_t mask_bstride, const float* table,
+                                    const float* noise2, uint64_t seed, uint64_t counter2, uint64_t offset,
+                                    void* stream) {
+    return cfd::guard([&] {
+        CFD_REQUIRE(sample && g_direct && g_unet && x_out && t && known && mask && table, CFD_EARG, "null argument");
+        CFD_REQUIRE(offset % 4 == 0, CFD_EARG, "noise offset must be a multiple of 4");
+        CFD_REQUIRE(n_per_sample > 0 && B > 0, CFD_EARG, "empty step");
+        CFD_REQUIRE((known_bstride == 0 || known_bstride == n_per_sample) &&
+                        (mask_bstride == 0 || mask_bstride == n_per_sample),
+                    CFD_EARG, "known rows and mask must be shared (stride 0) or per sample (stride n)");
+        const uintptr_t bits = (uintptr_t)sample | (uintptr_t)g_direct | (uintptr_t)g_unet | (uintptr_t)x_out |
+                               (uintptr_t)known | (uintptr_t)mask | (uintptr_t)noise2;
+        const int vec = (bits & 15) == 0 && n_per_sample % 4 == 0;
+        cfd::DpsKnownArgs a{sample, g_direct, g_unet, scale, x_out, t, n_per_sample, n_per_sample * B,
+                            seed, offset / 4, vec};
+        cfd::KnownArgs kn{known, mask, known_bstride, mask_bstride, table, noise2, counter2};
+        const int64_t groups = cfd::ceil_div(a.total, 4);
+        hipLaunchKernelGGL(cfd::dps_update_known_kernel, dim3((unsigned)cfd::ceil_div(groups, 256)), dim3(256), 0,
+                           (hipStream_t)stream, a, kn);
+        cfd::check_launch("dps_update_known_kernel");
     });
 }
 

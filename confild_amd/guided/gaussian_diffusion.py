@@ -39,6 +39,18 @@ batched call equals B single-sample calls, and samples shard over GPUs with no
 collective.  The measurement is shared by all samples ((T, Ns, c)) or given
 per sample ((B*T, Ns, c)).
 
+Known rows (no reference counterpart): ``known=, known_mask=, known_noise=`` hold
+latent rows to given values while the measurement guides the free ones.  Only the
+last call of the step changes: cfd_dps_update becomes
+
+    x       = cfd_dps_update_known(sample, g_direct, g_unet, scale, known, mask)
+
+which forms cfd_dps_update's image and then replaces it, where the mask is set, by
+the known rows at the noise level the step produces (q = a_i known + b_i n2, as
+GaussianDiffusion's known-row loops; n2 Philox (seed, (1 << 41) + k) or
+``known_noise``).  The gradient therefore acts on the free rows only.  'vanilla'
+runs cfd_sched_step_known.  Without ``known`` every call is the one above.
+
 RNG: as the unconditional sampler, Philox(seed, counter=step) by default, or the
 reference's draws through ``step_noise`` (the p_sample ``randn_like`` of every
 step; the unused q_sample draw of the noisy measurement is not needed).
@@ -51,8 +63,8 @@ import functools
 import torch
 
 from .. import _lib
-from ..gaussian_diffusion import (LossType, ModelMeanType, ModelVarType, STEP_DDIM, STEP_DDPM, broadcast_rows,
-                                  check_model_range, fresh_seed, get_named_beta_schedule)
+from ..gaussian_diffusion import (KNOWN_COUNTER, LossType, ModelMeanType, ModelVarType, STEP_DDIM, STEP_DDPM, _Known,
+                                  broadcast_rows, check_model_range, fresh_seed, get_named_beta_schedule)
 from ..respace import SpacedDiffusion, space_timesteps
 from .condition_methods import Identity, PosteriorSampling
 from .measurements import Case4Operator, InpaintingOperator
@@ -169,11 +181,15 @@ class _GuidedSampler(SpacedDiffusion):
         self.dense_budget = None  # workspace bytes the dense adjoint may plan for (None: the library default)
 
     def p_sample_loop(self, model, x_start, measurement, measurement_cond_fn, record=False, save_root=None, *,
-                      step_noise=None, seed=None, sample_offset=0, progress=False, resample=None):
+                      step_noise=None, seed=None, sample_offset=0, progress=False, resample=None, known=None,
+                      known_mask=None, known_noise=None):
         """gaussian_diffusion.py:169-206: guided reverse loop from x_start (B, 1, T, L).
         Per-step residual norms (the reference's progress-bar 'distance') are left in
-        ``self.distances`` (steps, B) on the GPU.  ``resample`` is refused: resampling
-        jumps belong to known-row replacement (GaussianDiffusion.p_sample_loop)."""
+        ``self.distances`` (steps, B) on the GPU.  ``known`` / ``known_mask`` (broadcast to
+        (1 | B, 1, T, L)): rows held to known values inside every step, as
+        GaussianDiffusion.p_sample_loop's; ``known_noise`` (steps, B, 1, T, L) replaces
+        their Philox normals.  ``resample`` is refused: resampling jumps belong to
+        known-row replacement (GaussianDiffusion.p_sample_loop)."""
         if resample is not None:
             raise ValueError("resampling jumps are not built for posterior sampling; use known-row replacement")
         if record:
@@ -182,6 +198,7 @@ class _GuidedSampler(SpacedDiffusion):
         if x_start.device.type != "cuda":
             raise _lib.CfdError("the DPS sampler runs on the GPU only (no CPU fallback)")
         mask = self._device_mask(method, kw, x_start, measurement)
+        kn = _Known.of(known, known_mask, known_noise, tuple(x_start.shape), x_start.device)
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
         x = x_start.detach().to(torch.float32).contiguous().clone()
@@ -192,23 +209,28 @@ class _GuidedSampler(SpacedDiffusion):
             indices = tqdm(indices)
         for k, i in enumerate(indices):
             nz = None if step_noise is None else step_noise[k]
+            nz2 = None if known_noise is None else known_noise[k]
             x = self._guided_step(model, x, i, measurement, method, nz, seed, k, sample_offset, self.distances[k],
-                                  mask)[0]
+                                  mask, kn, nz2)[0]
         check_model_range(model, x.device)
         return x
 
     def p_sample_step(self, model, x, index, measurement, measurement_cond_fn, noise=None, seed=None, counter=0,
-                      sample_offset=0):
+                      sample_offset=0, *, known=None, known_mask=None, known_noise=None):
         """One guided reverse step at respaced index ``index`` (p_sample + conditioning,
         gaussian_diffusion.py:188-199).  Returns dict(sample, pred_xstart, x_t, distance):
         the conditioned image, x0_hat, the unconditioned DDPM/DDIM sample, the norms.
-        Without ``noise`` and ``seed`` the step draws a fresh Philox key (fresh_seed)."""
+        Without ``noise`` and ``seed`` the step draws a fresh Philox key (fresh_seed).
+        ``known`` / ``known_mask`` / ``known_noise`` (one tensor of x's shape): as the loop's;
+        ``sample`` then carries the known rows, ``x_t`` stays the step's own sample."""
         method, kw = _method_of(measurement_cond_fn)
         seed = fresh_seed(noise, seed)
         x = x.detach().to(torch.float32).contiguous().clone()
+        kn = _Known.of(known, known_mask, known_noise, tuple(x.shape), x.device)
         dist = torch.zeros(x.shape[0], dtype=torch.float32, device=x.device)
         img, x0, sample = self._guided_step(model, x, index, measurement, method, noise, seed, counter,
-                                            sample_offset, dist, self._device_mask(method, kw, x, measurement))
+                                            sample_offset, dist, self._device_mask(method, kw, x, measurement), kn,
+                                            known_noise)
         return {"sample": img, "pred_xstart": x0, "x_t": sample, "distance": dist}
 
     @staticmethod
@@ -228,10 +250,28 @@ class _GuidedSampler(SpacedDiffusion):
         return _mask_tables(kw.get("mask"), op, x.shape[0], x.shape[2], op.coords.shape[0], op.model.out_features,
                             x.device)
 
+    def _update(self, sample, g_dir, g_unet, scale, t, seed, counter, offset, kn, nz2):
+        """The step's last call: cfd_dps_update, or with known rows (``kn`` a _Known)
+        cfd_dps_update_known, which also puts them back at the level the step produces."""
+        lib = _lib.lib()
+        st = _lib.stream_of(sample.device)
+        img = torch.empty_like(sample)
+        if kn is None:
+            _lib.check(lib.cfd_dps_update(_lib.ptr(sample), _lib.ptr(g_dir), _lib.ptr(g_unet), scale, _lib.ptr(img),
+                                          sample.numel(), st), "cfd_dps_update")
+            return img
+        _lib.check(lib.cfd_dps_update_known(_lib.ptr(sample), _lib.ptr(g_dir), _lib.ptr(g_unet), scale,
+                                            _lib.ptr(img), _lib.ptr(t), sample[0].numel(), sample.shape[0],
+                                            _lib.ptr(kn.known), kn.kstride, _lib.ptr(kn.mask), kn.mstride,
+                                            _lib.ptr(self._ktab(sample.device)), _lib.ptr(nz2), seed,
+                                            KNOWN_COUNTER + counter, offset, st), "cfd_dps_update_known")
+        return img
+
     def _guided_step(self, model, x, i, measurement, method, noise, seed, counter, sample_offset, dist_out,
-                     mask=None):
+                     mask=None, kn=None, known_noise=None):
         """x (B, 1, T, L) contiguous fp32 on the GPU; updated in place for 'ps'.
-        mask: None or the (1 | T | B*T, N, c) device tables of _mask_tables."""
+        mask: None or the (1 | T | B*T, N, c) device tables of _mask_tables.
+        kn: None or the _Known rows; known_noise: their normals (x's shape) or None."""
         dev = x.device
         if dev.type != "cuda":
             raise _lib.CfdError("the DPS sampler runs on the GPU only (no CPU fallback)")
@@ -246,11 +286,24 @@ class _GuidedSampler(SpacedDiffusion):
         t = torch.full((B,), i, dtype=torch.int64, device=dev)
         tm = self._map_timesteps(t)
         nz = None if noise is None else noise.to(device=dev, dtype=torch.float32).contiguous()
+        nz2 = None
+        if kn is not None and known_noise is not None:
+            nz2 = known_noise.to(device=dev, dtype=torch.float32).contiguous()
+            if nz2.shape != x.shape:
+                raise ValueError("known_noise must have the shape of x")
         dps = isinstance(method, PosteriorSampling)
         clip = 1 if self.clip_denoised else 0
         eps = (model.forward_tape(x, tm) if dps else model(x, tm)).contiguous()
         sample = torch.empty_like(x)
         x0 = torch.empty_like(x)
+        if kn is not None and not dps:
+            # 'vanilla': the unconditioned loops' known-row step
+            _lib.check(lib.cfd_sched_step_known(sched.handle, self._kind, clip, _lib.ptr(x), _lib.ptr(eps),
+                                                _lib.ptr(t), _lib.ptr(nz), seed, counter, offset, _lib.ptr(sample),
+                                                _lib.ptr(x0), n, B, _lib.ptr(kn.known), kn.kstride,
+                                                _lib.ptr(kn.mask), kn.mstride, _lib.ptr(self._ktab(dev)),
+                                                _lib.ptr(nz2), KNOWN_COUNTER + counter, st), "cfd_sched_step_known")
+            return sample, x0, sample
         _lib.check(lib.cfd_sched_step(sched.handle, self._kind, clip, _lib.ptr(x), _lib.ptr(eps), _lib.ptr(t),
                                       _lib.ptr(nz), seed, counter, offset, _lib.ptr(sample), _lib.ptr(x0), n, B, st),
                    "cfd_sched_step")
@@ -266,9 +319,7 @@ class _GuidedSampler(SpacedDiffusion):
                                                    _lib.ptr(mask.ws), mask.ws.numel() * 8, st),
                        "cfd_dps_latent_residual")
             g_unet = model.input_vjp(d_eps)
-            img = torch.empty_like(x)
-            _lib.check(lib.cfd_dps_update(_lib.ptr(sample), _lib.ptr(g_dir), _lib.ptr(g_unet), float(method.scale),
-                                          _lib.ptr(img), x.numel(), st), "cfd_dps_update")
+            img = self._update(sample, g_dir, g_unet, float(method.scale), t, seed, counter, offset, kn, nz2)
             return img, x0, sample
         y = measurement.to(device=dev, dtype=torch.float32).contiguous()
         vmax, vmin = op._bounds()
@@ -294,9 +345,7 @@ class _GuidedSampler(SpacedDiffusion):
                                            _lib.ptr(vmax), _lib.ptr(vmin), vmax.numel(), _lib.ptr(d_eps),
                                            _lib.ptr(g_dir), n, B, st), "cfd_dps_latent_grad")
         g_unet = model.input_vjp(d_eps)
-        img = torch.empty_like(x)
-        _lib.check(lib.cfd_dps_update(_lib.ptr(sample), _lib.ptr(g_dir), _lib.ptr(g_unet), float(method.scale),
-                                      _lib.ptr(img), x.numel(), st), "cfd_dps_update")
+        img = self._update(sample, g_dir, g_unet, float(method.scale), t, seed, counter, offset, kn, nz2)
         return img, x0, sample
 
 

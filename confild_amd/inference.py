@@ -18,9 +18,20 @@ reference-preserving defaults:
                                T_total = T + W * (T - rollout_overlap) rows, saved as
                                (B*T_total, N, c))
   rollout_overlap: T // 2     (rows a window shares with the sequence before it)
-  rollout_method: replace | ps   (replace: known-row replacement in the native loop;
-                               ps: posterior sampling with the 'inpainting' operator)
-  rollout_scale: 1.0          (the 'ps' step size)
+  rollout_method: replace | ps | guided   (replace: known-row replacement in the native loop;
+                               ps: posterior sampling with the 'inpainting' operator;
+                               guided: every window, window 0 included, is posterior sampling
+                               on its rows of a sensor record, and windows w >= 1 also hold
+                               their overlap rows to the sequence so far.  rollout_windows: 0
+                               then runs one guided window)
+  rollout_scale: 1.0          (the 'ps' / 'guided' step size)
+  rollout_sensor_coords:      ('guided', required: npy (Ns, d), the sensors' physical coordinates)
+  rollout_measurement:        ('guided', required: npy (T_total, Ns, c), the record in physical
+                               values, shared by the samples: the B samples are B posterior
+                               draws.  Any other row count is a ValueError before sampling)
+  rollout_sensor_mask: null   ('guided': npy (Ns, c) or (T_total, Ns, c), 1 where a value was measured)
+                               The operator is Case4Operator.from_parts on the driver's own CNF
+                               (network, x / y normalisers) and max_val / min_val.
   rollout_jump_length: 10     (RePaint resampling in the conditioned 'replace' windows: after every
   rollout_jump_n_sample: 1     jump_length levels the state is noised back up by jump_length levels
                                and re-denoised, jump_n_sample times in all, which harmonises free and
@@ -29,7 +40,8 @@ Known deviation (fixed on purpose): ``channel_mult`` from the YAML IS passed to
 create_model (the reference reads but drops it, inference.py:38-44, so its own
 case4.yml raises ValueError).
 
-Flow (inference.py:20-81): sample (B, 1, T, L) latents on the GPU(s) ->
+Flow (inference.py:20-81; with rollout_method: guided the CNF is loaded first,
+nothing else moves): sample (B, 1, T, L) latents on the GPU(s) ->
 de-normalise with max_val/min_val -> CNF decode of every latent row over the
 query points (one fused launch per chunk) -> np.save((B*T, N, c)) on rank 0.
 Multi-GPU: samples are sharded over ranks (dist.sharded_samples) with the
@@ -77,18 +89,60 @@ def unet_compute(inp) -> str:
 
 
 def rollout_sampler(inp, diff, sampler):
-    """(diffusion, method) of a rollout run: ``diff`` for 'replace', for 'ps' a guided
-    sampler on the same schedule (fixed-large variance, clipped x0, as ``diff`` runs)."""
+    """(diffusion, method) of a rollout run: ``diff`` for 'replace', for 'ps' and 'guided' a
+    guided sampler on the same schedule (fixed-large variance, clipped x0, as ``diff`` runs)."""
     method = str(getattr(inp, "rollout_method", "replace"))
     if method == "replace":
         return diff, method
-    if method != "ps":
-        raise ValueError(f"rollout_method must be 'replace' or 'ps', got {method!r}")
+    if method not in ("ps", "guided"):
+        raise ValueError(f"rollout_method must be 'replace', 'ps' or 'guided', got {method!r}")
     from .guided.gaussian_diffusion import create_sampler
     return create_sampler(sampler=sampler, steps=inp.steps, noise_schedule=inp.noise_schedule,
                           model_mean_type="epsilon", model_var_type="fixed_large", dynamic_threshold=False,
                           clip_denoised=True, rescale_timesteps=False,
                           timestep_respacing=getattr(inp, "timestep_respacing", "")), method
+
+
+def load_cnf(inp, device):
+    """The CNF decoder of the run on ``device`` (trainer: network and normalisers)."""
+    cnf = trainer(basic_input(inp.cnf_case_file_path), infer_mode=getattr(inp, "coords_path", None) is not None)
+    cnf.load(-1, siren_only=True)
+    cnf.nf.to(device)
+    return cnf
+
+
+def guided_rollout(inp, cnf, device, T, windows, overlap):
+    """{cond_fn, measurement} of ``rollout_method: guided``: a 'ps' method on a Case4Operator
+    built in memory from the driver's CNF and latent bounds, and the sensor record on
+    ``device``.  Shapes are checked here, before any sampling launch."""
+    from functools import partial
+
+    from .guided.condition_methods import get_conditioning_method
+    from .guided.measurements import Case4Operator, get_noise
+    from .rollout import plan_windows
+    for key in ("rollout_sensor_coords", "rollout_measurement"):
+        if getattr(inp, key, None) is None:
+            raise ValueError(f"rollout_method: guided needs {key}")
+    coords = np.load(inp.rollout_sensor_coords)
+    y = np.load(inp.rollout_measurement)
+    total = plan_windows(T, overlap, windows)[-1].stop
+    c = cnf.nf.out_features
+    if coords.ndim != 2 or y.shape != (total, coords.shape[0], c):
+        raise ValueError(f"rollout_measurement of shape {tuple(y.shape)} with rollout_sensor_coords of shape "
+                         f"{tuple(coords.shape)}: the record must be ({total}, Ns, {c}), T_total = {T} + "
+                         f"{windows} * ({T} - {overlap}) rows")
+    op = Case4Operator.from_parts(device, coords, cnf.in_normalizer, cnf.out_normalizer, cnf.nf, np.load(inp.max_val),
+                                  np.load(inp.min_val))
+    cond = get_conditioning_method("ps", op, get_noise("gaussian", sigma=0.0),
+                                   scale=float(getattr(inp, "rollout_scale", 1.0)))
+    fn = partial(cond.conditioning)
+    if getattr(inp, "rollout_sensor_mask", None) is not None:
+        mask = np.load(inp.rollout_sensor_mask)
+        if mask.shape not in ((coords.shape[0], c), y.shape):
+            raise ValueError(f"rollout_sensor_mask of shape {tuple(mask.shape)} is neither ({coords.shape[0]}, {c}) "
+                             f"nor {tuple(y.shape)}")
+        fn = partial(cond.conditioning, mask=torch.as_tensor(mask, dtype=torch.float32).to(device))
+    return {"cond_fn": fn, "measurement": torch.as_tensor(y, dtype=torch.float32).to(device)}
 
 
 def run(yaml_path: str):
@@ -122,8 +176,16 @@ def run(yaml_path: str):
     if windows < 0:
         raise ValueError(f"rollout_windows must be >= 0, got {windows}")
 
+    guided = str(getattr(inp, "rollout_method", "replace")) == "guided"
+    overlap = int(getattr(inp, "rollout_overlap", T // 2))
+    cnf, guide = None, {}
+    if guided:
+        # the measurement operator decodes with the driver's own CNF: load it before sampling
+        cnf = load_cnf(inp, device)
+        guide = guided_rollout(inp, cnf, device, T, windows, overlap)
+
     def sample(start, count):
-        if windows:
+        if windows or guided:
             from .rollout import extend_latents
             if (T, L) != (model.image_size, model.image_size):
                 raise ValueError("a rollout needs time_length == latent_length == image_size")
@@ -131,9 +193,10 @@ def run(yaml_path: str):
             rdiff, method = rollout_sampler(inp, diff, kind)
             n_sample = int(getattr(inp, "rollout_jump_n_sample", 1))
             resample = None if n_sample == 1 else (int(getattr(inp, "rollout_jump_length", 10)), n_sample)
-            return extend_latents(model, rdiff, None, windows, int(getattr(inp, "rollout_overlap", T // 2)), method,
+            return extend_latents(model, rdiff, None, windows, overlap, method,
                                   scale=float(getattr(inp, "rollout_scale", 1.0)), seed=loop_seed,
-                                  sample_offset=start, sampler=kind, batch_size=count, resample=resample)[:, 0]
+                                  sample_offset=start, sampler=kind, batch_size=count, resample=resample,
+                                  **guide)[:, 0]
         fn = diff.p_sample_loop if sampler == "ddpm" else diff.ddim_sample_loop
         return fn(model, (count, 1, T, L), seed=loop_seed, sample_offset=start)[:, 0]
 
@@ -144,9 +207,8 @@ def run(yaml_path: str):
     min_val = torch.as_tensor(np.load(inp.min_val), dtype=torch.float32).to(device).contiguous()
     gen = latent_denorm(gen.contiguous(), max_val, min_val)   # inference.py:59-61
 
-    cnf = trainer(basic_input(inp.cnf_case_file_path), infer_mode=getattr(inp, "coords_path", None) is not None)
-    cnf.load(-1, siren_only=True)
-    cnf.nf.to(device)
+    if cnf is None:
+        cnf = load_cnf(inp, device)
     coord = cnf.train_coord
     if getattr(inp, "coords_path", None):
         coord = torch.as_tensor(np.load(inp.coords_path), dtype=torch.float32)

@@ -284,6 +284,29 @@ int  cfd_dps_latent_grad(const cfd_sched* s, int clip, const float* x, const flo
                          float* d_eps, float* g_direct, int64_t n_per_sample, int B, void* stream);
 int  cfd_dps_update(const float* sample, const float* g_direct, const float* g_unet, float scale,
                     float* x_out, int64_t n, void* stream);
+/* cfd_dps_update followed by known-row replacement, in one launch (no reference
+ * counterpart): the last call of a DPS step whose sampler holds latent rows to
+ * known values.  Per element, fp contraction off, in this order:
+ *   img = sample - (g_direct + g_unet) * scale     cfd_dps_update's x_out, bit for bit
+ *   q   = a_i * known + b_i * n2                   (a_i, b_i) = row t[b] of table
+ *   out = m * q + (1 - m) * img                    cfd_sched_step_known's replacement, bit for bit
+ * so the gradient update acts where m = 0 and the known rows stand, at the noise
+ * level the step produces, where m = 1; at t[b] = 0, q = known.  t: (B) int64
+ * device indices into table ((n_t, 2) device fp32 rows, as cfd_sched_step_known's).
+ * known / mask: shared by the batch (stride 0) or per sample (stride n_per_sample).
+ * n2: noise2 (B*n device normals), or NULL for Philox (seed, counter2) at stream
+ * position offset + element (offset % 4 == 0): four elements per thread with
+ * cfd_sched_step_known's group offset, so the normals are the ones it draws for the
+ * same (seed, counter2, offset); the guided loop uses counter2 = (1 << 41) + k.
+ * Any n_per_sample (a last group of fewer than 4 elements included); arrays that
+ * are 16-byte aligned with n_per_sample % 4 == 0 take 16-byte loads and stores,
+ * the same bits.  x_out may alias sample.  CFD_EARG, and no launch, for a null
+ * array other than noise2, offset % 4 != 0, an empty step, or a stride that is
+ * neither 0 nor n_per_sample. */
+int  cfd_dps_update_known(const float* sample, const float* g_direct, const float* g_unet, float scale,
+                          float* x_out, const int64_t* t, int64_t n_per_sample, int B, const float* known,
+                          int64_t known_bstride, const float* mask, int64_t mask_bstride, const float* table,
+                          const float* noise2, uint64_t seed, uint64_t counter2, uint64_t offset, void* stream);
 /* The 'inpainting' operator under 'ps' (measurements.py:40-56: A(x0) = mask * x0 on
  * the latent image): what cfd_dps_residual and cfd_dps_latent_grad do for a SIREN
  * operator, in one call and without a decoder.  Per sample b:

@@ -1,0 +1,329 @@
+// Fused SIREN/FiLM decode with its coordinate Jacobian for gfx950 (K13).
+//
+// For each (latent row, query point): the value of the FiLM/SIREN chain
+// (N/cnf/nf_networks.py:480-495) and its forward-mode derivative with respect to
+// the physical coordinates, in one launch:
+//   layer 0  : u = w0 (W0 cn + F0);  X = sin(u);  T_k = w0 cos(u) * W0[:, k] s_k
+//   hidden i : u = w0 (W_i X + F_i); A_k = W_i T_k;  X = sin(u);  T_k = w0 cos(u) * A_k
+//   last     : out = W_L X + b_L;    J_k = W_L T_k
+//   physical : out_phys = denorm(out);  jac[b, n, o, k] = (ymax - ymin)[o] / 2 * J_k[o]
+// with cn = norm(x) and s_k = 2 / (xmax_k - xmin_k) (1 without a coordinate normaliser).
+//
+// Design (DESIGN.md "K13"): siren_fused's exact fp32 MFMA chain (siren.hip) with the
+// 1 + d chains of a point laid into the MFMA's 16 columns: column j16 = RS * point +
+// role, role 0 the value, roles 1..d the tangents (RS = 4: 4 points per wave, one
+// idle column per point at d = 2; RS = 2 at d = 1: 8 points x 2 roles).  The MFMA
+// treats its columns independently and the A operand (the weight block from the LDS
+// ring, streamed once per tile) is shared by all of them, so W_i X and every
+// W_i T_k come out of the same instructions.  Accumulators start at the FiLM vector
+// in the value column and at 0 in the tangent columns.  The only cross-column
+// traffic is the value column's pre-activation, which the tangent columns of its
+// group read with one DPP quad-permute move (no LDS); each lane then runs one range
+// reduction and one polynomial: the sine in the value column, the cosine in the
+// tangent columns (sincos_role below, bit for bit sin_cw / cos_cw of common.hpp).
+// Activations and tangents never leave registers; X[NB][4] / acc[NB] are
+// siren_fused's, so is the register budget.
+#include <algorithm>
+
+#include "siren.hpp"
+
+namespace cfd {
+
+struct SirenJacArgs {
+    const float* w0;      // (H, d)
+    const float* wimg;    // hidden weight image (as SirenArgs)
+    const float* wout;    // (c, H)
+    const float* bout;    // (c)
+    const float* film;    // (b, nh+1, H)
+    const float* coords;  // (N, d)
+    const float* xmax;
+    const float* xmin;
+    const float* ymax;
+    const float* ymin;
+    float* out;           // (b, N, c) or null
+    float* jac;           // (b, N, c, d)
+    int64_t N;
+    int64_t ystride;
+    int64_t b0;
+    int b;                // latent rows of the call (index assertions)
+    int d, c, nh;
+    float w0f;
+};
+
+// sin(x) where value is set, cos(x) elsewhere, from one reduction: sin_cw reduces by
+// q pi and cos_cw by an odd q' pi/2 with a split of pi/2 whose every term is exactly
+// half of sin_cw's, so fmaf(2q, c/2, x) == fmaf(q, c, x) bit for bit and both are
+// "x - qq * (pi/2 split)" with qq = 2q (sine) or q' (cosine); the polynomial is
+// shared.  sin: negate for odd q (qq & 2); cos: negate unless qq & 2.
+__device__ __forceinline__ float sincos_role(float x, bool value) {
+    const float t = fmaf(x, 0.318309886183790671538f, value ? 0.0f : -0.5f);
+    const float qq = fmaf(2.0f, rintf(t), value ? 0.0f : 1.0f);
+    float r = fmaf(qq, -1.5703125f, x);
+    r = fmaf(qq, -0.00048351287841796875f, r);
+    r = fmaf(qq, -3.13855707645416259765625e-07f, r);
+    r = fmaf(qq, -6.077100628276710381e-11f, r);
+    const float s = r * r;
+    float u = 2.6083159809786593541503e-06f;
+    u = fmaf(u, s, -0.0001981069071916863322258f);
+    u = fmaf(u, s, 0.00833307858556509017944336f);
+    u = fmaf(u, s, -0.166666597127914428710938f);
+    const float y = fmaf(s, u * r, r);
+    const bool neg = (((unsigned)(int)qq & 2u) != 0u) == value;
+    const float v = __uint_as_float(__float_as_uint(y) ^ (neg ? (1u << 31) : 0u));
+    const float xr = x * 0.159154943091895335768f;
+    const float hw = value ? __builtin_amdgcn_sinf(xr) : __builtin_amdgcn_cosf(xr);
+    return fabsf(x) < 39000.0f ? v : hw;
+}
+
+// the value column's copy of v within each group of RS columns (lanes of a group
+// are adjacent and groups never straddle a quad): DPP quad_perm, no LDS
+template <int RS>
+__device__ __forceinline__ float group_value(float v) {
+    constexpr int ctrl = RS == 4 ? 0x00 /* quad_perm [0,0,0,0] */ : 0xA0 /* quad_perm [0,0,2,2] */;
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), ctrl, 0xF, 0xF, false));
+}
+
+template <int NB, int RS, int WAVES>
+__global__ __launch_bounds__(64 * WAVES, NB <= 24 ? 2 : 1) void siren_jac_fused(SirenJacArgs p) {
+    constexpr int PPW = 16 / RS;       // points per wave
+    constexpr int TILE = PPW * WAVES;  // points per workgroup
+    constexpr int H = NB * 16;
+    constexpr int BLK = NB * 256;
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float* wbuf = smem;            // 2 ring slots
+    float* film = smem + 2 * BLK;  // (nh+1) x H, then w0 as (H, 4)
+
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    const int g = lane >> 4;
+    const int j16 = lane & 15;
+    const int role = j16 & (RS - 1);   // 0: value, k: d/dx_{k-1}
+    const bool value = role == 0;
+    const int64_t b = p.b0 + blockIdx.y;
+    const int64_t n = (int64_t)blockIdx.x * TILE + wave * PPW + j16 / RS;
+    const int64_t nc = n < p.N ? n : p.N - 1;
+    const int nh = p.nh;
+    const float w0f = p.w0f;
+    CFD_DASSERT(p.d >= 1 && p.d < RS && p.c >= 1 && p.c <= 4 && b < p.b && nc >= 0);
+
+    {
+        const float* fsrc = p.film + b * (int64_t)(nh + 1) * H;
+        const int nf = (nh + 1) * H;
+        for (int i = threadIdx.x * 4; i < nf; i += 64 * WAVES * 4) *(f4*)(film + i) = *(const f4*)(fsrc + i);
+    }
+    float* w0s = film + (nh + 1) * H;
+    for (int f = threadIdx.x; f < H; f += 64 * WAVES) {
+        f4 w = {0.f, 0.f, 0.f, 0.f};
+        for (int k = 0; k < p.d; ++k) w[k] = p.w0[f * p.d + k];
+        *(f4*)(w0s + 4 * f) = w;
+    }
+    // normalised coordinates; tsc = w0 * s_{role-1} for a live tangent column, else 0
+    float cn[3] = {0.f, 0.f, 0.f};
+    float tsc = 0.f;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        if (k < p.d) {
+            float v = p.coords[nc * p.d + k];
+            float sk = 1.0f;
+            if (p.xmax) {
+                const float hi = p.xmax[k], lo = p.xmin[k];
+                v = (v - lo) / (hi - lo) * 2.0f - 1.0f;
+                sk = 2.0f / (hi - lo);
+            }
+            cn[k] = v;
+            if (role == k + 1) tsc = w0f * sk;
+        }
+    }
+
+    __syncthreads();
+    if (nh > 0) siren_issue_block<NB, WAVES>(p.wimg, 0, wbuf, wave, lane);
+
+    // ---- layer 0 ----
+    float X[NB][4];
+    static_for<NB>([&](auto qc) {
+        constexpr int q = decltype(qc)::value;
+        const f4 fv = *(const f4*)(film + 16 * q + 4 * g);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const f4 w = *(const f4*)(w0s + 4 * (16 * q + 4 * g + r));
+            float a = cn[0] * w[0];
+#pragma unroll
+            for (int k = 1; k < 3; ++k)
+                if (k < p.d) a = fmaf(cn[k], w[k], a);
+            const float sc = sincos_role(w0f * (a + fv[r]), value);
+            const float wk = role == 1 ? w[0] : role == 2 ? w[1] : w[2];
+            X[q][r] = value ? sc : sc * (tsc * wk);
+        }
+    });
+
+    // ---- hidden layers: one fp32 MFMA chain carries the value and the tangents ----
+    const int nblocks = nh * NB;
+    int J = 0;
+    for (int layer = 1; layer <= nh; ++layer) {
+        f4 acc[NB];
+        static_for<NB>([&](auto jc) {
+            constexpr int j = decltype(jc)::value;
+            if (J + 1 < nblocks) siren_issue_block<NB, WAVES>(p.wimg, J + 1, wbuf + ((J + 1) & 1) * BLK, wave, lane);
+            const float* wb = wbuf + (J & 1) * BLK;
+            f4 a = *(const f4*)(film + layer * H + 16 * j + 4 * g);
+            if (!value) a = f4{0.f, 0.f, 0.f, 0.f};
+            static_for<NB>([&](auto qc) {
+                constexpr int q = decltype(qc)::value;
+                const f4 w = *(const f4*)(wb + (q * 64 + lane) * 4);
+                a = __builtin_amdgcn_mfma_f32_16x16x4f32(w.x, X[q][0], a, 0, 0, 0);
+                a = __builtin_amdgcn_mfma_f32_16x16x4f32(w.y, X[q][1], a, 0, 0, 0);
+                a = __builtin_amdgcn_mfma_f32_16x16x4f32(w.z, X[q][2], a, 0, 0, 0);
+                a = __builtin_amdgcn_mfma_f32_16x16x4f32(w.w, X[q][3], a, 0, 0, 0);
+            });
+            acc[j] = a;
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __syncthreads();
+            ++J;
+        });
+        static_for<NB>([&](auto qc) {
+            constexpr int q = decltype(qc)::value;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float av = acc[q][r];
+                const float sc = sincos_role(w0f * group_value<RS>(av), value);
+                X[q][r] = value ? sc : (w0f * sc) * av;
+            }
+        });
+    }
+
+    // ---- last layer (H -> c) per column; value: bias + de-normalisation, tangent: its slope ----
+    float o[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int oc = 0; oc < 4; ++oc) {
+        if (oc < p.c) {
+            const float* wr = p.wout + oc * H + 4 * g;
+            float s = 0.f;
+            static_for<NB>([&](auto qc) {
+                constexpr int q = decltype(qc)::value;
+                const f4 w = *(const f4*)(wr + 16 * q);
+                s = fmaf(w.x, X[q][0], s);
+                s = fmaf(w.y, X[q][1], s);
+                s = fmaf(w.z, X[q][2], s);
+                s = fmaf(w.w, X[q][3], s);
+            });
+            s += __shfl_xor(s, 16);
+            s += __shfl_xor(s, 32);
+            o[oc] = value ? s + p.bout[oc] : s;
+        }
+    }
+    if (n < p.N && g < p.c && role <= p.d) {
+        float v = g == 0 ? o[0] : g == 1 ? o[1] : g == 2 ? o[2] : o[3];
+        float hi = 1.0f, lo = -1.0f;
+        if (p.ymax) {
+            const int64_t yi = n * p.ystride + g;
+            hi = p.ymax[yi];
+            lo = p.ymin[yi];
+        }
+        const int64_t oi = (b * p.N + n) * p.c + g;
+        CFD_DASSERT(oi >= 0 && oi < (int64_t)p.b * p.N * p.c);
+        if (value) {
+            if (p.ymax) v = (v + 1.0f) / 2.0f * (hi - lo) + lo;
+            if (p.out) p.out[oi] = v;
+        } else {
+            if (p.ymax) v = v * ((hi - lo) / 2.0f);
+            const int64_t ji = oi * p.d + (role - 1);
+            CFD_DASSERT(ji >= 0 && ji < (int64_t)p.b * p.N * p.c * p.d);
+            p.jac[ji] = v;
+        }
+    }
+}
+
+}  // namespace cfd
+
+namespace {
+
+template <int NB, int RS>
+void launch_jac_nb(const cfd_siren* h, cfd::SirenJacArgs a, hipStream_t st) {
+    // 8 waves (2 per SIMD, 256 VGPRs each) share one weight stream; NB = 32 holds
+    // 128 + 128 registers of activations and accumulators alone, so it runs 4
+    // waves (1 per SIMD: 512 registers, the overflow in AGPRs, no scratch)
+    constexpr int WAVES = NB <= 24 ? 8 : 4, TILE = (16 / RS) * WAVES;
+    const int H = NB * 16;
+    const size_t lds = (size_t)(2 * NB * 256 + (h->cfg.num_hidden_layers + 1) * H + 4 * H) * sizeof(float);
+    const void* fn = (const void*)cfd::siren_jac_fused<NB, RS, WAVES>;
+    CFD_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const int64_t tiles = cfd::ceil_div(a.N, TILE);
+    CFD_REQUIRE(tiles <= 0x7fffffff, CFD_EARG, "too many query points for one call");
+    for (int64_t b0 = 0; b0 < a.b; b0 += 65535) {
+        a.b0 = b0;
+        const int nb = (int)std::min<int64_t>(65535, a.b - b0);
+        hipLaunchKernelGGL((cfd::siren_jac_fused<NB, RS, WAVES>), dim3((unsigned)tiles, nb), dim3(64 * WAVES), lds, st,
+                           a);
+        cfd::check_launch("siren_jac_fused");
+    }
+}
+
+template <int RS>
+void launch_jac(const cfd_siren* h, const cfd::SirenJacArgs& a, hipStream_t st) {
+    switch (h->NB) {
+        case 1: return launch_jac_nb<1, RS>(h, a, st);
+        case 2: return launch_jac_nb<2, RS>(h, a, st);
+        case 3: return launch_jac_nb<3, RS>(h, a, st);
+        case 4: return launch_jac_nb<4, RS>(h, a, st);
+        case 6: return launch_jac_nb<6, RS>(h, a, st);
+        case 8: return launch_jac_nb<8, RS>(h, a, st);
+        case 12: return launch_jac_nb<12, RS>(h, a, st);
+        case 16: return launch_jac_nb<16, RS>(h, a, st);
+        case 24: return launch_jac_nb<24, RS>(h, a, st);
+        case 32: return launch_jac_nb<32, RS>(h, a, st);
+        default: throw cfd::Error{CFD_EARG, "hidden_features must be 16*{1,2,3,4,6,8,12,16,24,32}"};
+    }
+}
+
+}  // namespace
+
+extern "C" int cfd_siren_jacobian_workspace_bytes(const cfd_siren* h, int b, size_t* bytes) {
+    return cfd_siren_workspace_bytes(h, b, bytes);   // the FiLM vectors (b, nh+1, H)
+}
+
+extern "C" int cfd_siren_forward_jacobian(cfd_siren* h, const float* coords, int64_t N, const float* latents, int b,
+                                          const float* xmax, const float* xmin, const float* ymax, const float* ymin,
+                                          int64_t y_stride, float* out, float* jac, void* ws, size_t ws_bytes,
+                                          void* stream) {
+    return cfd::guard([&] {
+        CFD_REQUIRE(h && coords && latents && jac, CFD_EARG, "null argument");
+        CFD_REQUIRE(N >= 1 && b >= 1, CFD_EARG, "empty decode");
+        CFD_REQUIRE((xmax == nullptr) == (xmin == nullptr), CFD_EARG, "xmax/xmin must both be set or both NULL");
+        CFD_REQUIRE((ymax == nullptr) == (ymin == nullptr), CFD_EARG, "ymax/ymin must both be set or both NULL");
+        const int d = h->cfg.in_coord_features;
+        CFD_REQUIRE(d <= 3, CFD_EARG,
+                    "cfd_siren_forward_jacobian: in_coord_features must be 1..3 (the 1 + d chains of a point share "
+                    "4 MFMA columns)");
+        size_t need = 0;
+        cfd_siren_jacobian_workspace_bytes(h, b, &need);
+        CFD_REQUIRE(ws && ws_bytes >= need, CFD_EARG, "workspace too small");
+        auto st = (hipStream_t)stream;
+        float* film = (float*)ws;
+        cfd::film_vectors(h, latents, b, film, st);
+        cfd::SirenJacArgs a{};
+        a.w0 = h->w0;
+        a.wimg = h->wimg;
+        a.wout = h->wout;
+        a.bout = h->bout;
+        a.film = film;
+        a.coords = coords;
+        a.xmax = xmax;
+        a.xmin = xmin;
+        a.ymax = ymax;
+        a.ymin = ymin;
+        a.out = out;
+        a.jac = jac;
+        a.N = N;
+        a.ystride = y_stride;
+        a.b = b;
+        a.d = d;
+        a.c = h->cfg.out_features;
+        a.nh = h->cfg.num_hidden_layers;
+        a.w0f = h->cfg.w0;
+        // always the exact fp32 chain, whatever the handle's compute mode
+        if (d == 1)
+            launch_jac<2>(h, a, st);
+        else
+            launch_jac<4>(h, a, st);
+    });
+}

@@ -36,6 +36,13 @@ reference-preserving defaults:
   rollout_jump_n_sample: 1     jump_length levels the state is noised back up by jump_length levels
                                and re-denoised, jump_n_sample times in all, which harmonises free and
                                known rows at (jump_n_sample - 1) more steps per level.  1: off)
+  derived: []                 (a subset of jacobian | vorticity | divergence | q_criterion: exact spatial
+                               derivatives of the decoded fields at the query points, from the fused
+                               value-and-Jacobian decode (trainer.infer_jacobian, confild_amd.derived).
+                               Each is saved beside save_path as <stem>_<name>.npy with the fields'
+                               leading shape: jacobian (..., c, d), vorticity (...) in 2-D or (..., 3),
+                               divergence and q_criterion (...).  The fields and out.npy do not change)
+  derived_velocity_channels:  (which d output channels are the velocity, default the first d)
 Known deviation (fixed on purpose): ``channel_mult`` from the YAML IS passed to
 create_model (the reference reads but drops it, inference.py:38-44, so its own
 case4.yml raises ValueError).
@@ -50,6 +57,7 @@ fields are gathered to rank 0.
 """
 from __future__ import annotations
 
+import os
 import sys
 
 import numpy as np
@@ -101,6 +109,29 @@ def rollout_sampler(inp, diff, sampler):
                           model_mean_type="epsilon", model_var_type="fixed_large", dynamic_threshold=False,
                           clip_denoised=True, rescale_timesteps=False,
                           timestep_respacing=getattr(inp, "timestep_respacing", "")), method
+
+
+DERIVED = ("jacobian", "vorticity", "divergence", "q_criterion")
+
+
+def derived_names(inp):
+    """The ``derived`` YAML key as a list of names (empty: today's run)."""
+    names = getattr(inp, "derived", None) or []
+    if isinstance(names, str):
+        names = [names]
+    names = [str(n) for n in names]
+    bad = [n for n in names if n not in DERIVED]
+    if bad or len(set(names)) != len(names):
+        raise ValueError(f"derived must be distinct names out of {list(DERIVED)}, got {names}")
+    return names
+
+
+def derived_quantity(name, jac, velocity_channels=None):
+    """One ``derived`` quantity of a Jacobian (..., c, d)."""
+    from . import derived
+    if name == "jacobian":
+        return jac
+    return getattr(derived, name)(jac, velocity_channels)
 
 
 def load_cnf(inp, device):
@@ -218,19 +249,35 @@ def run(yaml_path: str):
     spatial = tuple(coord.shape[:-1])
     npts = int(np.prod(spatial))
     lat = gen.reshape(B * T, L)
-    # rows per launch bounded by ~2 GiB of output
-    rows = max(1, (2 << 30) // (npts * cnf.nf.out_features * 4))
-    fields = []
+    names = derived_names(inp)
+    vch = getattr(inp, "derived_velocity_channels", None)
+    c, d = cnf.nf.out_features, cnf.nf.in_coord_features
+    # rows per launch bounded by ~2 GiB of output (with `derived`: the fields and their (c, d) Jacobian)
+    rows = max(1, (2 << 30) // (npts * c * 4 * (1 + d if names else 1)))
+    fields, extra = [], {n: [] for n in names}
     s, e = dist.shard_range(B * T, rank, world)
     for a in range(s, e, rows):
-        fields.append(cnf.infer(coord, lat[a:min(e, a + rows)]))
-    local = torch.cat(fields) if fields else torch.empty((0,) + spatial + (cnf.nf.out_features,), device=device)
+        chunk = lat[a:min(e, a + rows)]
+        # the fields are the plain decode's whether or not `derived` is set (the Jacobian
+        # launch is always the exact fp32 chain; its values are not the ones saved)
+        fields.append(cnf.infer(coord, chunk))
+        if names:
+            jac = cnf.infer_jacobian(coord, chunk)[1]
+            for n in names:
+                extra[n].append(derived_quantity(n, jac, vch))
+    local = {"": torch.cat(fields) if fields else torch.empty((0,) + spatial + (c,), device=device)}
+    for n in names:
+        local[n] = (torch.cat(extra[n]) if extra[n] else
+                    derived_quantity(n, torch.empty((0,) + spatial + (c, d), device=device), vch)).contiguous()
     if world > 1:   # gather the decoded fields to rank 0 over RCCL
         sizes = [dist.shard_range(B * T, r, world)[1] - dist.shard_range(B * T, r, world)[0] for r in range(world)]
-        local = dist.gather_cat(local, 0, sizes, dst=0)
+        local = {n: dist.gather_cat(v, 0, sizes, dst=0) for n, v in local.items()}
     if rank == 0:
-        out = local.cpu().numpy()
+        out = local[""].cpu().numpy()
         np.save(inp.save_path, out)                          # (B*T, N, c) or (B*T, h, w, c), inference.py:79-81
+        stem = os.path.splitext(str(inp.save_path))[0]
+        for n in names:
+            np.save(f"{stem}_{n}.npy", local[n].cpu().numpy())
         return out
     return None
 

@@ -244,6 +244,36 @@ class SIRENAutodecoder_film(nn.Module):
             out = post.denormalize(out)
         return out.reshape((b,) + spatial + (c,))
 
+    # -- value and coordinate Jacobian (K13: cfd_siren_forward_jacobian) ------------
+    def decode_jacobian(self, coords, latents, x_normalizer=None, y_normalizer=None):
+        """decode() together with its exact spatial derivatives, one fused launch:
+        returns (out (b, *spatial, c), jac (b, *spatial, c, d)) with jac[..., o, k] =
+        d out[..., o] / d coords[..., k], both in physical units (the chain rule through
+        the normalisers is applied).  Broadcasting as decode().  Always the exact fp32
+        chain, whatever set_compute chose.  Only '-11' normalisers (fused)."""
+        d, L, c = self.in_coord_features, self.in_latent_features, self.out_features
+        dev = latents.device
+        if dev.type != "cuda":
+            raise _lib.CfdError("SIREN decode_jacobian needs GPU tensors (the HIP path has no CPU fallback)")
+        cf, lat, spatial = self._flatten(coords, latents, d, L)
+        cf = cf.to(device=dev, dtype=torch.float32).contiguous()
+        lat = lat.detach().to(torch.float32).contiguous()
+        N, b = cf.shape[0], lat.shape[0]
+        cf, xmax, xmin, ymax, ymin, ystride, post = self._norm_args(cf, N, dev, x_normalizer, y_normalizer)
+        if post is not None or (x_normalizer is not None and xmax is None):
+            raise NotImplementedError("the SIREN coordinate Jacobian fuses '-11' normalisers only")
+        h, lib = self._handle(dev), _lib.load()
+        nbytes = C.c_size_t()
+        _lib.check(lib.cfd_siren_jacobian_workspace_bytes(h, b, C.byref(nbytes)), "siren jacobian workspace")
+        ws = torch.empty(max(nbytes.value, 16), dtype=torch.uint8, device=dev)
+        out = torch.empty((b, N, c), dtype=torch.float32, device=dev)
+        jac = torch.empty((b, N, c, d), dtype=torch.float32, device=dev)
+        _lib.check(lib.cfd_siren_forward_jacobian(h, _lib.ptr(cf), N, _lib.ptr(lat), b, _lib.ptr(xmax),
+                                                  _lib.ptr(xmin), _lib.ptr(ymax), _lib.ptr(ymin), ystride,
+                                                  _lib.ptr(out), _lib.ptr(jac), _lib.ptr(ws), ws.numel(),
+                                                  _lib.stream_of(dev)), "cfd_siren_forward_jacobian")
+        return out.reshape((b,) + spatial + (c,)), jac.reshape((b,) + spatial + (c, d))
+
     # -- latent gradient at a few query points (DPS measurement operator) ---------
     def tape_forward(self, coords, latents, x_normalizer=None, y_normalizer=None):
         """decode() of R latent rows (R, L) at Ns points (Ns, d) -> (R, Ns, c), keeping the

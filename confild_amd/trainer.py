@@ -81,6 +81,17 @@ class trainer:
             return self.nf.decode(coord, latents.reshape(latents.shape[0], -1)[:, None],
                                   self.in_normalizer, self.out_normalizer)
 
+    def infer_jacobian(self, coord, latents):
+        """infer() with the fields' exact spatial derivatives: (fields (b, N, c), jac
+        (b, N, c, d)) (or (b, h, w, c) / (b, h, w, c, d) for grid coordinates), jac =
+        d fields / d coord in physical units (SIRENAutodecoder_film.decode_jacobian)."""
+        coord = coord if coord is not None else self.train_coord
+        if coord is None:
+            raise ValueError("no query coordinates: pass coord (infer_mode=True has no training points)")
+        with torch.no_grad():
+            return self.nf.decode_jacobian(coord, latents.reshape(latents.shape[0], -1)[:, None],
+                                           self.in_normalizer, self.out_normalizer)
+
     def load(self, checkpoint_id: int, siren_only=False):
         """train.py:481-528: newest checkpoint_*.pt when checkpoint_id == -1."""
         save = self.hyper_para.save_path

@@ -373,6 +373,21 @@ int  cfd_siren_forward(cfd_siren* h, const float* coords, int64_t N, const float
                        const float* xmax, const float* xmin,
                        const float* ymax, const float* ymin, int64_t y_stride,
                        float* out, void* workspace, size_t ws_bytes, void* stream);
+/* cfd_siren_forward together with its coordinate Jacobian, one fused launch
+ * (csrc/siren_jac.hip): jac (b, N, c, d), jac[b, n, o, k] = d out[b, n, o] /
+ * d coords[n, k] in physical units on both sides (the chain rule through both
+ * normalisers is applied: 2 / (xmax_k - xmin_k) in, (ymax - ymin) / 2 out).
+ * Arguments, normaliser forms (y_stride 0 or c, NULL pairs), workspace and error
+ * codes as cfd_siren_forward; out may be NULL (only the Jacobian is stored).
+ * Always the exact fp32 MFMA chain, whatever cfd_siren_set_compute chose; the
+ * bits of a (latent row, point) pair depend on neither b, N, the point's index
+ * nor the other rows.  in_coord_features = 4 returns CFD_EARG. */
+int  cfd_siren_jacobian_workspace_bytes(const cfd_siren* h, int b, size_t* bytes);
+int  cfd_siren_forward_jacobian(cfd_siren* h, const float* coords, int64_t N, const float* latents, int b,
+                                const float* xmax, const float* xmin,
+                                const float* ymax, const float* ymin, int64_t y_stride,
+                                float* out, float* jac,
+                                void* workspace, size_t ws_bytes, void* stream);
 
 /* Latent-gradient of the Case4 measurement operator (DPS; replaces autograd
  * through Case4Operator.forward -> pass_through_model_batch -> SIRENAutodecoder_film,

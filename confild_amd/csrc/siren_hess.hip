@@ -1,0 +1,393 @@
+// Fused SIREN/FiLM decode with its coordinate Jacobian and Hessian for gfx950 (K14).
+//
+// For each (latent row, query point): the value of the FiLM/SIREN chain, its d
+// forward-mode tangents and its second-order (Taylor-mode) chains with respect to the
+// physical coordinates, in one launch.  With a_k = W0[:, k] s_k:
+//   layer 0  : u = w0 (W0 cn + F0);  X = sin u;  T_k = w0 cos u * a_k
+//              S_kl = -w0^2 sin u * a_k a_l
+//   hidden i : u = w0 (W_i X + F_i); A_k = W_i T_k;  H_kl = W_i S_kl   (one MFMA chain)
+//              X = sin u;  T_k = w0 cos u * A_k
+//              S_kl = w0 cos u * H_kl - w0^2 sin u * A_k A_l
+//   last     : out = W_L X + b_L;  J_k = W_L T_k;  G_kl = W_L S_kl
+//   physical : out, jac as K13;  hess[b, n, o, k, l] = (ymax - ymin)[o] / 2 * G_kl[o]
+// with cn = norm(x) and s_k = 2 / (xmax_k - xmin_k) (1 without a coordinate normaliser).
+//
+// Design (DESIGN.md "K14"): K13's chain (siren_jac.hip) with more roles per point.
+// Column j16 = RS * point + role: role 0 the value, roles 1..d the tangents, then the
+// nsec second-order roles (the d diagonal ones xx, yy, zz first, then xy, xz, yz);
+// the remaining columns of a group carry zeros.  RS = 4 at d = 1 (4 points per wave),
+// 8 at d = 2 and for the diagonal at d = 3 (2 points), 16 for the full Hessian at
+// d = 3 (1 point).  Every chain is linear through W_i, so all of them come out of the
+// same MFMAs on one stream of the weights.  A second-order column needs three values
+// of other columns of its group per element and layer: the value column's
+// pre-activation and the pre-activations A_k, A_l of two tangent columns; its sine it
+// computes itself, and the cosine is the one a tangent column of the group has just
+// computed for the same argument.  A group lies inside a 16-lane row, and the four
+// arrive by ds_bpermute_b32 (the LDS crossbar, no LDS memory).  Value and tangent columns evaluate K13's expressions;
+// the second-order update is one fixed fmaf sequence, the same in every instantiation.
+#include <algorithm>
+
+#include "siren.hpp"
+
+namespace cfd {
+
+struct SirenHessArgs {
+    const float* w0;      // (H, d)
+    const float* wimg;    // hidden weight image (as SirenArgs)
+    const float* wout;    // (c, H)
+    const float* bout;    // (c)
+    const float* film;    // (b, nh+1, H)
+    const float* coords;  // (N, d)
+    const float* xmax;
+    const float* xmin;
+    const float* ymax;
+    const float* ymin;
+    float* out;           // (b, N, c) or null
+    float* jac;           // (b, N, c, d) or null
+    float* hess;          // (b, N, c, d, d), or (b, N, c, d) with diag
+    int64_t N;
+    int64_t ystride;
+    int64_t b0;
+    int b;                // latent rows of the call (index assertions)
+    int d, c, nh;
+    int nsec;             // second-order roles: d (diagonal only) or d (d + 1) / 2
+    int diag;             // hess holds the diagonal only
+    float w0f;
+};
+
+// sin(x) where value is set, cos(x) elsewhere, from one reduction (K13's sincos_role,
+// bit for bit sin_cw / cos_cw of common.hpp): "x - qq * (pi/2 split)" with qq = 2q
+// (sine) or the odd q' (cosine), one shared polynomial; sin: negate for odd q
+// (qq & 2), cos: negate unless qq & 2.
+__device__ __forceinline__ float hess_sincos_role(float x, bool value) {
+    const float t = fmaf(x, 0.318309886183790671538f, value ? 0.0f : -0.5f);
+    const float qq = fmaf(2.0f, rintf(t), value ? 0.0f : 1.0f);
+    float r = fmaf(qq, -1.5703125f, x);
+    r = fmaf(qq, -0.00048351287841796875f, r);
+    r = fmaf(qq, -3.13855707645416259765625e-07f, r);
+    r = fmaf(qq, -6.077100628276710381e-11f, r);
+    const float s = r * r;
+    float u = 2.6083159809786593541503e-06f;
+    u = fmaf(u, s, -0.0001981069071916863322258f);
+    u = fmaf(u, s, 0.00833307858556509017944336f);
+    u = fmaf(u, s, -0.166666597127914428710938f);
+    const float y = fmaf(s, u * r, r);
+    const bool neg = (((unsigned)(int)qq & 2u) != 0u) == value;
+    const float v = __uint_as_float(__float_as_uint(y) ^ (neg ? (1u << 31) : 0u));
+    const float xr = x * 0.159154943091895335768f;
+    const float hw = value ? __builtin_amdgcn_sinf(xr) : __builtin_amdgcn_cosf(xr);
+    return fabsf(x) < 39000.0f ? v : hw;
+}
+
+// v of the lane whose byte address (4 * lane) is addr: ds_bpermute_b32, no LDS memory
+__device__ __forceinline__ float lane_value(int addr, float v) {
+    return __int_as_float(__builtin_amdgcn_ds_bpermute(addr, __float_as_int(v)));
+}
+
+// the second-order update of one element, one fixed order for every form:
+// w0 cos u * h - ((w0^2 sin u) * ak) * al
+__device__ __forceinline__ float second_order(float w0f, float w0sq, float su, float cu, float h, float ak,
+                                              float al) {
+    const float t = ((w0sq * su) * ak) * al;
+    return fmaf(w0f * cu, h, -t);
+}
+
+template <int NB, int RS, int WAVES>
+__global__ __launch_bounds__(64 * WAVES, NB <= 24 ? 2 : 1) void siren_hess_fused(SirenHessArgs p) {
+    constexpr int PPW = 16 / RS;       // points per wave
+    constexpr int TILE = PPW * WAVES;  // points per workgroup
+    constexpr int H = NB * 16;
+    constexpr int BLK = NB * 256;
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float* wbuf = smem;            // 2 ring slots
+    float* film = smem + 2 * BLK;  // (nh+1) x H, then w0 as (H, 4)
+
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    const int g = lane >> 4;
+    const int j16 = lane & 15;
+    const int role = j16 & (RS - 1);
+    const int d = p.d;
+    const int sidx = role - 1 - d;     // index among the second-order roles
+    const bool value = role == 0;
+    const bool tangent = role >= 1 && role <= d;
+    const bool second = sidx >= 0 && sidx < p.nsec;
+    // the coordinates (k, l), k <= l, of this column: tangent k = l = role - 1; second
+    // order xx, yy, zz, then xy, xz, yz
+    int ck = 0, cl = 0;
+    if (tangent) ck = cl = role - 1;
+    if (second) {
+        const int pr = sidx - d;
+        ck = pr < 0 ? sidx : pr == 2 ? 1 : 0;
+        cl = pr < 0 ? sidx : pr == 0 ? 1 : 2;
+    }
+    // byte addresses (ds_bpermute) of the group's value column, of tangents k and l and
+    // of the column whose cosine this one reads
+    const int base = lane - role;
+    const int src_v = 4 * base;
+    const int src_k = second ? 4 * (base + 1 + ck) : 4 * lane;
+    const int src_l = second ? 4 * (base + 1 + cl) : 4 * lane;
+    const int src_c = 4 * (base + 1);  // the first tangent column: cos u
+    const int64_t b = p.b0 + blockIdx.y;
+    const int64_t n = (int64_t)blockIdx.x * TILE + wave * PPW + j16 / RS;
+    const int64_t nc = n < p.N ? n : p.N - 1;
+    const int nh = p.nh;
+    const float w0f = p.w0f;
+    const float w0sq = w0f * w0f;
+    CFD_DASSERT(d >= 1 && d <= 3 && 1 + d + p.nsec <= RS && p.c >= 1 && p.c <= 4 && b < p.b && nc >= 0);
+    CFD_DASSERT(ck <= cl && cl < d && src_v >= 0 && src_k >= 0 && src_k < 256 && src_l >= 0 && src_l < 256);
+
+    {
+        const float* fsrc = p.film + b * (int64_t)(nh + 1) * H;
+        const int nf = (nh + 1) * H;
+        for (int i = threadIdx.x * 4; i < nf; i += 64 * WAVES * 4) *(f4*)(film + i) = *(const f4*)(fsrc + i);
+    }
+    float* w0s = film + (nh + 1) * H;
+    for (int f = threadIdx.x; f < H; f += 64 * WAVES) {
+        f4 w = {0.f, 0.f, 0.f, 0.f};
+        for (int k = 0; k < d; ++k) w[k] = p.w0[f * d + k];
+        *(f4*)(w0s + 4 * f) = w;
+    }
+    // normalised coordinates; tsc = w0 * s_k for a tangent column (K13's), sk / sl the
+    // coordinate scales of a second-order column
+    float cn[3] = {0.f, 0.f, 0.f};
+    float tsc = 0.f, sk = 0.f, sl = 0.f;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        if (k < d) {
+            float v = p.coords[nc * d + k];
+            float s = 1.0f;
+            if (p.xmax) {
+                const float hi = p.xmax[k], lo = p.xmin[k];
+                v = (v - lo) / (hi - lo) * 2.0f - 1.0f;
+                s = 2.0f / (hi - lo);
+            }
+            cn[k] = v;
+            if (tangent && ck == k) tsc = w0f * s;
+            if (second && ck == k) sk = s;
+            if (second && cl == k) sl = s;
+        }
+    }
+
+    __syncthreads();
+    if (nh > 0) siren_issue_block<NB, WAVES>(p.wimg, 0, wbuf, wave, lane);
+
+    // ---- layer 0 ----
+    float X[NB][4];
+    static_for<NB>([&](auto qc) {
+        constexpr int q = decltype(qc)::value;
+        const f4 fv = *(const f4*)(film + 16 * q + 4 * g);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const f4 w = *(const f4*)(w0s + 4 * (16 * q + 4 * g + r));
+            float a = cn[0] * w[0];
+#pragma unroll
+            for (int k = 1; k < 3; ++k)
+                if (k < d) a = fmaf(cn[k], w[k], a);
+            // sine in the value and second-order columns, cosine in the tangent columns
+            const float sc = hess_sincos_role(w0f * (a + fv[r]), !tangent);
+            const float wk = ck == 0 ? w[0] : ck == 1 ? w[1] : w[2];
+            const float wl = cl == 0 ? w[0] : cl == 1 ? w[1] : w[2];
+            const float sv = second_order(w0f, w0sq, sc, 0.0f, 0.0f, wk * sk, wl * sl);
+            X[q][r] = value ? sc : tangent ? sc * (tsc * wk) : second ? sv : 0.0f;
+        }
+    });
+
+    // ---- hidden layers: one fp32 MFMA chain carries every role ----
+    const int nblocks = nh * NB;
+    int J = 0;
+    for (int layer = 1; layer <= nh; ++layer) {
+        f4 acc[NB];
+        static_for<NB>([&](auto jc) {
+            constexpr int j = decltype(jc)::value;
+            if (J + 1 < nblocks) siren_issue_block<NB, WAVES>(p.wimg, J + 1, wbuf + ((J + 1) & 1) * BLK, wave, lane);
+            const float* wb = wbuf + (J & 1) * BLK;
+            f4 a = *(const f4*)(film + layer * H + 16 * j + 4 * g);
+            if (!value) a = f4{0.f, 0.f, 0.f, 0.f};
+            static_for<NB>([&](auto qc) {
+                constexpr int q = decltype(qc)::value;
+                const f4 w = *(const f4*)(wb + (q * 64 + lane) * 4);
+                a = __builtin_amdgcn_mfma_f32_16x16x4f32(w.x, X[q][0], a, 0, 0, 0);
+                a = __builtin_amdgcn_mfma_f32_16x16x4f32(w.y, X[q][1], a, 0, 0, 0);
+                a = __builtin_amdgcn_mfma_f32_16x16x4f32(w.z, X[q][2], a, 0, 0, 0);
+                a = __builtin_amdgcn_mfma_f32_16x16x4f32(w.w, X[q][3], a, 0, 0, 0);
+            });
+            acc[j] = a;
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __syncthreads();
+            ++J;
+        });
+        static_for<NB>([&](auto qc) {
+            constexpr int q = decltype(qc)::value;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float av = acc[q][r];
+                const float x = w0f * lane_value(src_v, av);
+                const float ak = lane_value(src_k, av);
+                const float al = lane_value(src_l, av);
+                // one reduction and one polynomial per lane: the sine in the value and
+                // second-order columns, the cosine in the tangent columns, from where the
+                // second-order columns fetch it (tangent 0 of the group has it for the same x)
+                const float sc = hess_sincos_role(x, !tangent);
+                const float cu = lane_value(src_c, sc);
+                const float sv = second_order(w0f, w0sq, sc, cu, av, ak, al);
+                X[q][r] = value ? sc : tangent ? (w0f * sc) * av : second ? sv : 0.0f;
+            }
+        });
+    }
+
+    // ---- last layer (H -> c) per column; value: bias + de-normalisation, others: their slope ----
+    float o[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int oc = 0; oc < 4; ++oc) {
+        if (oc < p.c) {
+            const float* wr = p.wout + oc * H + 4 * g;
+            float s = 0.f;
+            static_for<NB>([&](auto qc) {
+                constexpr int q = decltype(qc)::value;
+                const f4 w = *(const f4*)(wr + 16 * q);
+                s = fmaf(w.x, X[q][0], s);
+                s = fmaf(w.y, X[q][1], s);
+                s = fmaf(w.z, X[q][2], s);
+                s = fmaf(w.w, X[q][3], s);
+            });
+            s += __shfl_xor(s, 16);
+            s += __shfl_xor(s, 32);
+            o[oc] = value ? s + p.bout[oc] : s;
+        }
+    }
+    if (n < p.N && g < p.c && (value || tangent || second)) {
+        float v = g == 0 ? o[0] : g == 1 ? o[1] : g == 2 ? o[2] : o[3];
+        float hi = 1.0f, lo = -1.0f;
+        if (p.ymax) {
+            const int64_t yi = n * p.ystride + g;
+            hi = p.ymax[yi];
+            lo = p.ymin[yi];
+        }
+        const int64_t oi = (b * p.N + n) * p.c + g;
+        [[maybe_unused]] const int64_t no = (int64_t)p.b * p.N * p.c;
+        CFD_DASSERT(oi >= 0 && oi < no);
+        if (value) {
+            if (p.ymax) v = (v + 1.0f) / 2.0f * (hi - lo) + lo;
+            if (p.out) p.out[oi] = v;
+        } else {
+            if (p.ymax) v = v * ((hi - lo) / 2.0f);
+            if (tangent) {
+                const int64_t ji = oi * d + ck;
+                CFD_DASSERT(ji >= 0 && ji < no * d);
+                if (p.jac) p.jac[ji] = v;
+            } else if (p.diag) {
+                const int64_t di = oi * d + ck;
+                CFD_DASSERT(di >= 0 && di < no * d);
+                if (ck == cl) p.hess[di] = v;
+            } else {
+                // both halves from the same lane: symmetric to the bit
+                const int64_t h0 = (oi * d + ck) * d + cl, h1 = (oi * d + cl) * d + ck;
+                CFD_DASSERT(h0 >= 0 && h0 < no * d * d && h1 >= 0 && h1 < no * d * d);
+                p.hess[h0] = v;
+                if (ck != cl) p.hess[h1] = v;
+            }
+        }
+    }
+}
+
+}  // namespace cfd
+
+namespace {
+
+template <int NB, int RS>
+void launch_hess_nb(const cfd_siren* h, cfd::SirenHessArgs a, hipStream_t st) {
+    // K13's workgroup shapes: 8 waves (2 per SIMD) share one weight stream; NB = 32
+    // runs 4 waves (1 per SIMD, the overflow in AGPRs)
+    constexpr int WAVES = NB <= 24 ? 8 : 4, TILE = (16 / RS) * WAVES;
+    const int H = NB * 16;
+    const size_t lds = (size_t)(2 * NB * 256 + (h->cfg.num_hidden_layers + 1) * H + 4 * H) * sizeof(float);
+    const void* fn = (const void*)cfd::siren_hess_fused<NB, RS, WAVES>;
+    CFD_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const int64_t tiles = cfd::ceil_div(a.N, TILE);
+    CFD_REQUIRE(tiles <= 0x7fffffff, CFD_EARG, "too many query points for one call");
+    for (int64_t b0 = 0; b0 < a.b; b0 += 65535) {
+        a.b0 = b0;
+        const int nb = (int)std::min<int64_t>(65535, a.b - b0);
+        hipLaunchKernelGGL((cfd::siren_hess_fused<NB, RS, WAVES>), dim3((unsigned)tiles, nb), dim3(64 * WAVES), lds, st,
+                           a);
+        cfd::check_launch("siren_hess_fused");
+    }
+}
+
+template <int RS>
+void launch_hess(const cfd_siren* h, const cfd::SirenHessArgs& a, hipStream_t st) {
+    switch (h->NB) {
+        case 1: return launch_hess_nb<1, RS>(h, a, st);
+        case 2: return launch_hess_nb<2, RS>(h, a, st);
+        case 3: return launch_hess_nb<3, RS>(h, a, st);
+        case 4: return launch_hess_nb<4, RS>(h, a, st);
+        case 6: return launch_hess_nb<6, RS>(h, a, st);
+        case 8: return launch_hess_nb<8, RS>(h, a, st);
+        case 12: return launch_hess_nb<12, RS>(h, a, st);
+        case 16: return launch_hess_nb<16, RS>(h, a, st);
+        case 24: return launch_hess_nb<24, RS>(h, a, st);
+        case 32: return launch_hess_nb<32, RS>(h, a, st);
+        default: throw cfd::Error{CFD_EARG, "hidden_features must be 16*{1,2,3,4,6,8,12,16,24,32}"};
+    }
+}
+
+}  // namespace
+
+extern "C" int cfd_siren_hessian_workspace_bytes(const cfd_siren* h, int b, size_t* bytes) {
+    return cfd_siren_workspace_bytes(h, b, bytes);   // the FiLM vectors (b, nh+1, H)
+}
+
+extern "C" int cfd_siren_forward_hessian(cfd_siren* h, const float* coords, int64_t N, const float* latents, int b,
+                                         const float* xmax, const float* xmin, const float* ymax, const float* ymin,
+                                         int64_t y_stride, float* out, float* jac, float* hess, int diag_only, void* ws,
+                                         size_t ws_bytes, void* stream) {
+    return cfd::guard([&] {
+        CFD_REQUIRE(h && coords && latents && hess, CFD_EARG, "null argument");
+        CFD_REQUIRE(N >= 1 && b >= 1, CFD_EARG, "empty decode");
+        CFD_REQUIRE((xmax == nullptr) == (xmin == nullptr), CFD_EARG, "xmax/xmin must both be set or both NULL");
+        CFD_REQUIRE((ymax == nullptr) == (ymin == nullptr), CFD_EARG, "ymax/ymin must both be set or both NULL");
+        const int d = h->cfg.in_coord_features;
+        CFD_REQUIRE(d <= 3, CFD_EARG,
+                    "cfd_siren_forward_hessian: in_coord_features must be 1..3 (the value, tangent and second-order "
+                    "chains of a point share 16 MFMA columns)");
+        size_t need = 0;
+        cfd_siren_hessian_workspace_bytes(h, b, &need);
+        CFD_REQUIRE(ws && ws_bytes >= need, CFD_EARG, "workspace too small");
+        auto st = (hipStream_t)stream;
+        float* film = (float*)ws;
+        cfd::film_vectors(h, latents, b, film, st);
+        cfd::SirenHessArgs a{};
+        a.w0 = h->w0;
+        a.wimg = h->wimg;
+        a.wout = h->wout;
+        a.bout = h->bout;
+        a.film = film;
+        a.coords = coords;
+        a.xmax = xmax;
+        a.xmin = xmin;
+        a.ymax = ymax;
+        a.ymin = ymin;
+        a.out = out;
+        a.jac = jac;
+        a.hess = hess;
+        a.N = N;
+        a.ystride = y_stride;
+        a.b = b;
+        a.d = d;
+        a.c = h->cfg.out_features;
+        a.nh = h->cfg.num_hidden_layers;
+        a.diag = diag_only != 0;
+        a.w0f = h->cfg.w0;
+        // always the exact fp32 chain, whatever the handle's compute mode.  d <= 2 runs
+        // the full form for both outputs; d = 3 has a diagonal form of 8 columns per point
+        const bool full = d < 3 || !a.diag;
+        a.nsec = full ? d * (d + 1) / 2 : d;
+        if (d == 1)
+            launch_hess<4>(h, a, st);
+        else if (d == 2 || !full)
+            launch_hess<8>(h, a, st);
+        else
+            launch_hess<16>(h, a, st);
+    });
+}

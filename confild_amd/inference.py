@@ -41,7 +41,12 @@ reference-preserving defaults:
                                value-and-Jacobian decode (trainer.infer_jacobian, confild_amd.derived).
                                Each is saved beside save_path as <stem>_<name>.npy with the fields'
                                leading shape: jacobian (..., c, d), vorticity (...) in 2-D or (..., 3),
-                               divergence and q_criterion (...).  The fields and out.npy do not change)
+                               divergence and q_criterion (...).  The fields and out.npy do not change.
+                               Also hessian | laplacian | grad_divergence: exact second derivatives from
+                               the fused value-Jacobian-Hessian decode (trainer.infer_hessian), one more
+                               launch per chunk, which leaves the files above as they are: hessian
+                               (..., c, d, d), laplacian (..., c), grad_divergence (..., d).  laplacian
+                               alone runs the diagonal form)
   derived_velocity_channels:  (which d output channels are the velocity, default the first d)
 Known deviation (fixed on purpose): ``channel_mult`` from the YAML IS passed to
 create_model (the reference reads but drops it, inference.py:38-44, so its own
@@ -111,7 +116,8 @@ def rollout_sampler(inp, diff, sampler):
                           timestep_respacing=getattr(inp, "timestep_respacing", "")), method
 
 
-DERIVED = ("jacobian", "vorticity", "divergence", "q_criterion")
+HESSIAN_DERIVED = ("hessian", "laplacian", "grad_divergence")      # from infer_hessian, the rest from infer_jacobian
+DERIVED = ("jacobian", "vorticity", "divergence", "q_criterion") + HESSIAN_DERIVED
 
 
 def derived_names(inp):
@@ -126,11 +132,18 @@ def derived_names(inp):
     return names
 
 
-def derived_quantity(name, jac, velocity_channels=None):
-    """One ``derived`` quantity of a Jacobian (..., c, d)."""
+def derived_quantity(name, jac, velocity_channels=None, hess=None, diag=False):
+    """One ``derived`` quantity of a Jacobian (..., c, d) or, for HESSIAN_DERIVED, of a
+    Hessian (..., c, d, d) (``diag``: its diagonal form (..., c, d), enough for laplacian)."""
     from . import derived
     if name == "jacobian":
         return jac
+    if name == "hessian":
+        return hess
+    if name == "laplacian":
+        return derived.laplacian(hess, diag=diag)
+    if name == "grad_divergence":
+        return derived.grad_divergence(hess, velocity_channels)
     return getattr(derived, name)(jac, velocity_channels)
 
 
@@ -252,8 +265,13 @@ def run(yaml_path: str):
     names = derived_names(inp)
     vch = getattr(inp, "derived_velocity_channels", None)
     c, d = cnf.nf.out_features, cnf.nf.in_coord_features
-    # rows per launch bounded by ~2 GiB of output (with `derived`: the fields and their (c, d) Jacobian)
-    rows = max(1, (2 << 30) // (npts * c * 4 * (1 + d if names else 1)))
+    jnames = [n for n in names if n not in HESSIAN_DERIVED]
+    hnames = [n for n in names if n in HESSIAN_DERIVED]
+    diag = hnames == ["laplacian"]                           # the unmixed derivatives are all it needs
+    hd = d if diag else d * d
+    # rows per launch bounded by ~2 GiB of output (with `derived`: the fields and their (c, d) Jacobian;
+    # with a Hessian name also that launch's fields, Jacobian and (c, d, d) or (c, d) Hessian)
+    rows = max(1, (2 << 30) // (npts * c * 4 * ((1 + d if jnames else 1) + (1 + d + hd if hnames else 0))))
     fields, extra = [], {n: [] for n in names}
     s, e = dist.shard_range(B * T, rank, world)
     for a in range(s, e, rows):
@@ -261,14 +279,20 @@ def run(yaml_path: str):
         # the fields are the plain decode's whether or not `derived` is set (the Jacobian
         # launch is always the exact fp32 chain; its values are not the ones saved)
         fields.append(cnf.infer(coord, chunk))
-        if names:
+        if jnames:
             jac = cnf.infer_jacobian(coord, chunk)[1]
-            for n in names:
+            for n in jnames:
                 extra[n].append(derived_quantity(n, jac, vch))
+        if hnames:
+            hess = cnf.infer_hessian(coord, chunk, diag=diag)[2]
+            for n in hnames:
+                extra[n].append(derived_quantity(n, None, vch, hess, diag))
     local = {"": torch.cat(fields) if fields else torch.empty((0,) + spatial + (c,), device=device)}
     for n in names:
         local[n] = (torch.cat(extra[n]) if extra[n] else
-                    derived_quantity(n, torch.empty((0,) + spatial + (c, d), device=device), vch)).contiguous()
+                    derived_quantity(n, torch.empty((0,) + spatial + (c, d), device=device), vch,
+                                     torch.empty((0,) + spatial + (c,) + (d,) * (1 if diag else 2), device=device),
+                                     diag)).contiguous()
     if world > 1:   # gather the decoded fields to rank 0 over RCCL
         sizes = [dist.shard_range(B * T, r, world)[1] - dist.shard_range(B * T, r, world)[0] for r in range(world)]
         local = {n: dist.gather_cat(v, 0, sizes, dst=0) for n, v in local.items()}

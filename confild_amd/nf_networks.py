@@ -274,6 +274,41 @@ class SIRENAutodecoder_film(nn.Module):
                                                   _lib.stream_of(dev)), "cfd_siren_forward_jacobian")
         return out.reshape((b,) + spatial + (c,)), jac.reshape((b,) + spatial + (c, d))
 
+    # -- value, Jacobian and coordinate Hessian (K14: cfd_siren_forward_hessian) ------
+    def decode_hessian(self, coords, latents, x_normalizer=None, y_normalizer=None, diag=False):
+        """decode_jacobian() together with the exact second spatial derivatives, one
+        fused launch: returns (out, jac, hess) with hess (b, *spatial, c, d, d),
+        hess[..., o, k, l] = d2 out[..., o] / d coords[..., k] d coords[..., l] in
+        physical units, symmetric to the bit; ``diag=True`` returns (b, *spatial, c, d),
+        the unmixed derivatives alone (all a Laplacian needs: half the columns at d = 3).
+        Broadcasting, normalisers and compute mode as decode_jacobian()."""
+        d, L, c = self.in_coord_features, self.in_latent_features, self.out_features
+        dev = latents.device
+        if dev.type != "cuda":
+            raise _lib.CfdError("SIREN decode_hessian needs GPU tensors (the HIP path has no CPU fallback)")
+        cf, lat, spatial = self._flatten(coords, latents, d, L)
+        cf = cf.to(device=dev, dtype=torch.float32).contiguous()
+        lat = lat.detach().to(torch.float32).contiguous()
+        N, b = cf.shape[0], lat.shape[0]
+        cf, xmax, xmin, ymax, ymin, ystride, post = self._norm_args(cf, N, dev, x_normalizer, y_normalizer)
+        if post is not None or (x_normalizer is not None and xmax is None):
+            raise NotImplementedError("the SIREN coordinate Hessian fuses '-11' normalisers only")
+        h, lib = self._handle(dev), _lib.load()
+        nbytes = C.c_size_t()
+        _lib.check(lib.cfd_siren_hessian_workspace_bytes(h, b, C.byref(nbytes)), "siren hessian workspace")
+        ws = torch.empty(max(nbytes.value, 16), dtype=torch.uint8, device=dev)
+        hshape = (c, d) if diag else (c, d, d)
+        out = torch.empty((b, N, c), dtype=torch.float32, device=dev)
+        jac = torch.empty((b, N, c, d), dtype=torch.float32, device=dev)
+        hess = torch.empty((b, N) + hshape, dtype=torch.float32, device=dev)
+        _lib.check(lib.cfd_siren_forward_hessian(h, _lib.ptr(cf), N, _lib.ptr(lat), b, _lib.ptr(xmax),
+                                                 _lib.ptr(xmin), _lib.ptr(ymax), _lib.ptr(ymin), ystride,
+                                                 _lib.ptr(out), _lib.ptr(jac), _lib.ptr(hess), int(bool(diag)),
+                                                 _lib.ptr(ws), ws.numel(), _lib.stream_of(dev)),
+                   "cfd_siren_forward_hessian")
+        return (out.reshape((b,) + spatial + (c,)), jac.reshape((b,) + spatial + (c, d)),
+                hess.reshape((b,) + spatial + hshape))
+
     # -- latent gradient at a few query points (DPS measurement operator) ---------
     def tape_forward(self, coords, latents, x_normalizer=None, y_normalizer=None):
         """decode() of R latent rows (R, L) at Ns points (Ns, d) -> (R, Ns, c), keeping the

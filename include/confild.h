@@ -388,6 +388,21 @@ int  cfd_siren_forward_jacobian(cfd_siren* h, const float* coords, int64_t N, co
                                 const float* ymax, const float* ymin, int64_t y_stride,
                                 float* out, float* jac,
                                 void* workspace, size_t ws_bytes, void* stream);
+/* The same with the second derivatives, one fused launch (csrc/siren_hess.hip):
+ * hess (b, N, c, d, d), hess[b, n, o, k, l] = d2 out[b, n, o] / d coords[n, k]
+ * d coords[n, l] in physical units (the coordinate scales of both axes and
+ * (ymax - ymin) / 2 applied), symmetric to the bit; with diag_only != 0 hess is
+ * (b, N, c, d), the unmixed derivatives d2 / d coords[n, k]^2 alone, with the bits
+ * of the full form's diagonal.  out (b, N, c) and jac (b, N, c, d) may each be
+ * NULL (that store is skipped); hess is required.  Arguments, normaliser forms,
+ * workspace and error codes as cfd_siren_forward_jacobian; always the exact fp32
+ * MFMA chain; in_coord_features = 4 returns CFD_EARG before any launch. */
+int  cfd_siren_hessian_workspace_bytes(const cfd_siren* h, int b, size_t* bytes);
+int  cfd_siren_forward_hessian(cfd_siren* h, const float* coords, int64_t N, const float* latents, int b,
+                               const float* xmax, const float* xmin,
+                               const float* ymax, const float* ymin, int64_t y_stride,
+                               float* out, float* jac, float* hess, int diag_only,
+                               void* workspace, size_t ws_bytes, void* stream);
 
 /* Latent-gradient of the Case4 measurement operator (DPS; replaces autograd
  * through Case4Operator.forward -> pass_through_model_batch -> SIRENAutodecoder_film,

@@ -1170,6 +1170,25 @@ void pack_split_f16(cfd_siren* h, int li, const float* W) {
                     }
         CFD_HIP(hipMemcpy(h->wimg32r + (size_t)(li - 1) * NB * NB * 256, img.data(),
                           img.size() * sizeof(_Float16), hipMemcpyHostToDevice));
+        // the same scaled values and halves for the 16x16x32 form of siren_split32:
+        // slot J (32 rows), step k = 2q + rb (K-chunk q of 32 features, row block rb of
+        // 16 rows): 1 KiB of hi then 1 KiB of lo, lane l element t =
+        // W[32J + 16 rb + l%16][16(2q + t/4) + 4(l/16) + t%4] (pack_split_f16's k order)
+        for (int J = 0; J < NB2; ++J)
+            for (int k = 0; k < NK; ++k)
+                for (int l = 0; l < 64; ++l)
+                    for (int t = 0; t < 8; ++t) {
+                        const int q = k / 2, rb = k % 2;
+                        const double v = (double)W[(size_t)(32 * J + 16 * rb + l % 16) * H + 16 * (2 * q + t / 4) +
+                                                   4 * (l / 16) + t % 4] * kr * sr;
+                        const _Float16 hi = (_Float16)v;
+                        const _Float16 lo = (_Float16)(v - (double)hi);
+                        const size_t base = ((size_t)J * NK + k) * 1024 + l * 8 + t;
+                        img[base] = hi;
+                        img[base + 512] = lo;
+                    }
+        CFD_HIP(hipMemcpy(h->wimg16r + (size_t)(li - 1) * NB * NB * 256, img.data(),
+                          img.size() * sizeof(_Float16), hipMemcpyHostToDevice));
         const int nh = h->cfg.num_hidden_layers;
         const float fs = (float)(kr * sr), inv = (float)(1.0 / sr);
         CFD_HIP(hipMemcpy(h->wrev + (li - 1), &fs, sizeof(float), hipMemcpyHostToDevice));
@@ -1218,6 +1237,7 @@ extern "C" int cfd_siren_create(const cfd_siren_cfg* cfg, int device, cfd_siren*
         CFD_HIP(hipMalloc(&h->wimg32, sizeof(float) * (size_t)std::max(nh, 1) * NB * NB * 256));
         CFD_HIP(hipMalloc(&h->wimg32r, sizeof(float) * (size_t)std::max(nh, 1) * NB * NB * 256));
         CFD_HIP(hipMalloc(&h->wrev, sizeof(float) * 2 * (size_t)std::max(nh, 1)));
+        CFD_HIP(hipMalloc(&h->wimg16r, sizeof(float) * (size_t)std::max(nh, 1) * NB * NB * 256));
         *out = h;
     });
 }
@@ -1237,6 +1257,7 @@ extern "C" void cfd_siren_destroy(cfd_siren* h) {
     (void)hipFree(h->wimg32);
     (void)hipFree(h->wimg32r);
     (void)hipFree(h->wrev);
+    (void)hipFree(h->wimg16r);
     delete h;
 }
 
@@ -1380,6 +1401,7 @@ extern "C" int cfd_siren_forward(cfd_siren* h, const float* coords, int64_t N, c
             if (cfd::siren_split32_supported(H, nh)) {   // K7t; K7s for the other widths
                 a.wimg = h->wimg32;
                 a.wimg_rev = h->wimg32r;
+                a.wimg_rev16 = h->wimg16r;
                 a.wrev = h->wrev;
                 cfd::launch_siren_split32(H, a, b, st);
             } else {

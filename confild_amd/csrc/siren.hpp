@@ -36,6 +36,7 @@ struct SirenArgs {
     const float* wscale;  // (nh) power-of-two weight scale of each hidden layer (split-f16 image only)
     const float* wimg_rev; // siren_split32 image of the hidden weights pre-scaled by (w0 / 2pi) s'_i (HWSIN >= 3)
     const float* wrev;     // (2 nh): FiLM scale (w0 / 2pi) s'_i of each hidden layer, then 1 / s'_i
+    const float* wimg_rev16; // the same values as wimg_rev in the 16x16x32 form's order (siren_split32, SHAPE 16)
     int64_t N;
     int64_t ystride;
     int64_t b0;           // first latent of this launch (grid.y chunking)
@@ -143,6 +144,7 @@ struct cfd_siren {
     float* wimg32 = nullptr; // the same split in the 32x32x16 chain's k order (siren_split32)
     float* wimg32r = nullptr; // siren_split32 image of W (w0 / 2pi) s'_i: accumulators in revolutions
     float* wrev = nullptr;    // (2 nh): (w0 / 2pi) s'_i, then 1 / s'_i
+    float* wimg16r = nullptr; // wimg32r's words in the order of siren_split32's 16x16x32 form
     int compute = CFD_SIREN_SPLIT_F16;
     int dense_bwd = CFD_DENSE_BWD_SUM;          // dense DPS adjoint forms (dps_dense.hip,
     int dense_compute = CFD_DENSE_COMPUTE_AUTO;  // cfd_siren_dense_set_form)

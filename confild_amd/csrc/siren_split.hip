@@ -427,11 +427,17 @@ __global__ __launch_bounds__(64 * WAVES, CG == 1 ? 2 : 1) void siren_fused_split
 // ---------------------------------------------------------------------------
 // K7t: the same split-f16 chain on v_mfma_f32_32x32x16_f16, one wave per SIMD.
 //
-// Why: the 16x16x32 chain above is issue-bound, not MFMA-bound.  A 16x16x32
-// MFMA holds the SIMD's vector issue for 8 of its 16 cycles, and each fp32
-// activation needs ~15 VALU instructions (scale, sine, split) -- together more
-// issue than the MFMA time they hide behind.  A 32x32x16 MFMA holds issue for 8
-// of its 32 cycles at the same FLOP rate, which halves the hold per FLOP.
+// Why: the 16x16x32 chain above (K7s) is issue-bound, not MFMA-bound.  A 16x16x32
+// MFMA holds the SIMD's vector issue for 8 of its 16 cycles, and with K7s's
+// polynomial sine each fp32 activation needs ~15 VALU instructions (scale, sine,
+// split) -- together more issue than the MFMA time they hide behind.  A 32x32x16
+// MFMA holds issue for 8 of its 32 cycles at the same FLOP rate, which halves the
+// hold per FLOP.  With v_sin_f32 on revolutions and the v_fma_mix split (4.5 VALU
+// per activation) that no longer decides: this kernel's 16x16x32 form
+// (split16_body below) spends more cycles (+10 % wall on a clock-capped CU half
+// alone) and is faster by wall time on the whole chip at H >= 128, because the
+// power-bound chip holds a higher clock on that shape (1.57 -> 1.87 GHz at
+// H = 384).  H = 64 stays on this form.
 //
 // Layout: workgroup = 4 waves x 32 coordinates, one latent (grid.y).  Output
 // block J (32 features) of a layer is one 32x32 accumulator: lane (h = l/32,
@@ -469,8 +475,19 @@ __device__ __forceinline__ void split_chunk(const float (&x)[16], int e, Frag& h
 // EXP (timing experiments only, wrong results): bit 0 no weight streaming / barrier,
 // bit 1 no sine (x = scaled accumulator), bit 2 no per-step A-fragment LDS reads
 // (every step reuses the block's first fragments)
-template <int NB2, int EXP = 0, int HWSIN = 0>
-__global__ __launch_bounds__(256, 1) void siren_split32(SirenArgs p) {
+// One fp32 fma as one v_fma_f32.  The output-layer sums run beside MFMAs, where the
+// compiler's SLP packing of adjacent scalar fmas (v_pk_fma_f32 plus the v_mov_b32
+// that pair its operands: 32 + 48 per block of the last layer) costs more issue
+// than the 64 scalar instructions (MI355X_MICROARCH.md, filler prices).  Same
+// operation, same bits.
+__device__ __forceinline__ float fma_scalar(float a, float b, float c) {
+    float d;
+    asm("v_fma_f32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c));
+    return d;
+}
+
+template <int NB2, int EXP, int HWSIN>
+__device__ __forceinline__ void split32_body(const SirenArgs& p) {
     constexpr int NK = 2 * NB2;    // 16-deep K chunks per layer
     constexpr int H = 32 * NB2;
     constexpr int BLK = NK * 512;  // floats per 32-row block: NK x {hi, lo} x 1 KiB
@@ -604,7 +621,7 @@ __global__ __launch_bounds__(256, 1) void siren_split32(SirenArgs p) {
             for (int oc = 0; oc < 4; ++oc) {
                 const f4 w = *(const f4*)(wos + oc * H + f);
 #pragma unroll
-                for (int r = 0; r < 4; ++r) o[oc] = fmaf(w[r], x[4 * e + r], o[oc]);
+                for (int r = 0; r < 4; ++r) o[oc] = fma_scalar(w[r], x[4 * e + r], o[oc]);
             }
         };
         static_for<NB2>([&](auto jc) {
@@ -740,6 +757,296 @@ __global__ __launch_bounds__(256, 1) void siren_split32(SirenArgs p) {
 #endif
 }
 
+// The same kernel on v_mfma_f32_16x16x32_f16 (SHAPE 16): same workgroup (4 waves x
+// 32 coordinates x one latent), grid, ring, DMA, barrier placement and epilogue
+// pipeline; only the tile's inside differs.  A wave's 32 coordinates are two column
+// groups of 16: lane (n = l%16, g = l/16) serves coordinates n and 16 + n.  A ring
+// slot (32 rows) is two 16-row blocks rb; its NK steps are k = 2q + rb, K-chunk q
+// (32 features) of row block rb: one A fragment pair shared by both groups, six
+// MFMAs on the two accumulators (rb, c).  Lane (n, g) holds features
+// 32J + 16 rb + 4g + r of slot J in acc[rb][c][r], which are exactly elements
+// t = 4 rb + r of the next layer's K-chunk J for group c (siren_fused_split's
+// accumulator-is-next-B layout; image: pack_split_f16's k order, wimg_rev16).  The
+// last chunk of a layer, split at steps 16-17 of the next layer's first slot, is
+// consumed at its steps NK-2, NK-1 (q = NB2-1), as in the 32x32x16 form.
+template <int NB2, int EXP, int HWSIN>
+__device__ __forceinline__ void split16_body(const SirenArgs& p) {
+    constexpr int NQ = NB2;        // 32-deep K chunks per layer
+    constexpr int NK = 2 * NB2;    // steps per slot
+    constexpr int H = 32 * NB2;
+    constexpr int BLK = NK * 512;  // floats per 32-row slot: NK x {hi, lo} x 1 KiB
+    constexpr int WAVES = 4, TILE = 128;
+    constexpr int NPC = 2 * NK;
+    constexpr int PPW = NPC / WAVES;
+    constexpr int NKS = NK >= 18 ? 16 : NK - 2;
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int nh = p.nh;
+    float* wbuf = smem;                // 2 ring slots
+    float* film = smem + 2 * BLK;      // (nh+1) x H; hidden layers' rows pre-scaled
+    float* w0s = film + (nh + 1) * H;  // (H, 4)
+    float* wos = w0s + 4 * H;          // (4, H)
+
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int g = lane >> 4;
+    const int64_t b = p.b0 + blockIdx.y;
+    const int64_t n0 = (int64_t)blockIdx.x * TILE + wave * 32 + (lane & 15);  // + 16 c
+    CFD_DASSERT(p.d >= 1 && p.d <= 4 && p.c >= 1 && p.c <= 4 && nh >= 1);
+#ifdef CFD_STAMPS
+    const bool stamped = blockIdx.x % 61 == 0;
+    if (stamped) CFD_STAMP(p.stamps, 5, (unsigned)blockIdx.y, 0);
+    __builtin_amdgcn_s_waitcnt(0xC07F);
+#endif
+
+    {
+        const float* fsrc = p.film + b * (int64_t)(nh + 1) * H;
+        const int nf = (nh + 1) * H;
+        for (int i = threadIdx.x * 4; i < nf; i += 64 * WAVES * 4) {
+            const int layer = i / H;
+            const float sc = layer == 0 ? 1.0f : HWSIN >= 3 ? p.wrev[layer - 1] : p.wscale[layer - 1];
+            *(f4*)(film + i) = *(const f4*)(fsrc + i) * sc;
+        }
+    }
+    for (int f = threadIdx.x; f < H; f += 64 * WAVES) {
+        f4 w = {0.f, 0.f, 0.f, 0.f};
+        for (int k = 0; k < p.d; ++k) w[k] = p.w0[f * p.d + k];
+        *(f4*)(w0s + 4 * f) = w;
+    }
+    for (int i = threadIdx.x; i < 4 * H; i += 64 * WAVES) wos[i] = i < p.c * H ? p.wout[i] : 0.f;
+    // a group past the last point computes point N - 1 again (never stored)
+    float cn[2][4];
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+        const int64_t n = n0 + 16 * c;
+        const int64_t nc = n < p.N ? n : p.N - 1;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            float v = 0.f;
+            if (k < p.d) {
+                v = p.coords[nc * p.d + k];
+                if (p.xmax) v = (v - p.xmin[k]) / (p.xmax[k] - p.xmin[k]) * 2.0f - 1.0f;
+            }
+            cn[c][k] = v;
+        }
+    }
+    __syncthreads();
+    const int nblocks = nh * NB2;
+    const __amdgpu_buffer_rsrc_t wrsrc =
+        __builtin_amdgcn_make_buffer_rsrc((void*)p.wimg, 0, nblocks * (BLK * 4), 0x00020000);
+    siren_issue_block<NPC, WAVES>(p.wimg, 0, wbuf, wave, lane);
+
+    // operand sets, group c's chunk q at [c * NQ + q]
+    Frag BH[NK], BL[NK], NH[NK], NL[NK];
+    float o[2][4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+
+    // ---- layer 0 (d -> H, fp32 VALU), into the split set; x[8c + 4rb + r] ----
+    static_for<NB2>([&](auto Jc) {
+        constexpr int J = decltype(Jc)::value;
+        float x[16];
+#pragma unroll
+        for (int rb = 0; rb < 2; ++rb) {
+            const f4 fv = *(const f4*)(film + 32 * J + 16 * rb + 4 * g);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const f4 w = *(const f4*)(w0s + 4 * (32 * J + 16 * rb + 4 * g + r));
+#pragma unroll
+                for (int c = 0; c < 2; ++c) {
+                    float a = cn[c][0] * w[0];
+#pragma unroll
+                    for (int k = 1; k < 4; ++k)
+                        if (k < p.d) a = fmaf(cn[c][k], w[k], a);
+                    x[8 * c + 4 * rb + r] = hidden_sine<HWSIN >= 2 ? 2 : HWSIN>(p.w0f * (a + fv[r]));
+                }
+            }
+        }
+        split_chunk(x, 0, NH[J], NL[J]);
+        split_chunk(x, 1, NH[NQ + J], NL[NQ + J]);
+    });
+
+    static_assert(NB2 % 2 == 0, "static ring slots need an even block count");
+    int J = 0;
+    float prev[16];   // the slot before: [8c + 4rb + r]
+#pragma unroll
+    for (int v = 0; v < 16; ++v) prev[v] = 0.f;
+    float mprev = 0.f;
+    float x[16];
+    h8 FH, FL;
+    f4 an[2][2];      // [rb][c]
+    // the FiLM row of both groups: one read per accumulator (the second group's off an
+    // address the compiler cannot merge with the first's, so no register copies)
+    int g1 = g;
+    asm volatile("" : "+v"(g1));
+    auto film_row = [&](const float* frow) __attribute__((always_inline)) {
+#pragma unroll
+        for (int rb = 0; rb < 2; ++rb) {
+            an[rb][0] = *(const f4*)(frow + 16 * rb + 4 * g);
+            an[rb][1] = *(const f4*)(frow + 16 * rb + 4 * g1);
+        }
+    };
+    if constexpr (!(EXP & 1)) {
+        __builtin_amdgcn_s_waitcnt(vmcnt_imm(0));
+        asm volatile("s_barrier" ::: "memory");
+    }
+    FH = *(const h8*)(wbuf + lane * 4);
+    FL = *(const h8*)(wbuf + 256 + lane * 4);
+    for (int layer = 1; layer <= nh; ++layer) {
+        const bool last = layer == nh;
+        const float m = HWSIN >= 3 ? p.wrev[nh + layer - 1] : p.w0f / p.wscale[layer - 1];
+        // output-layer partial sums over the 4 features of row block rb of slot jp, group c
+        auto outsum = [&](int jp, int c, int rb) __attribute__((always_inline)) {  // wos rows oc >= c are zero
+            const int f = 32 * jp + 16 * rb + 4 * g;
+#pragma unroll
+            for (int oc = 0; oc < 4; ++oc) {
+                const f4 w = *(const f4*)(wos + oc * H + f);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) o[c][oc] = fma_scalar(w[r], x[8 * c + 4 * rb + r], o[c][oc]);
+            }
+        };
+        static_for<NB2>([&](auto jc) {
+            constexpr int j = decltype(jc)::value;
+            constexpr int jp = j == 0 ? NB2 - 1 : j - 1;
+            const float me = j == 0 ? mprev : m;
+            const bool live = j > 0 || layer > 1;
+            float* nxt = wbuf + ((j & 1) ^ 1) * BLK;
+            const float* wb = wbuf + (j & 1) * BLK;
+            const int soff = __builtin_amdgcn_readfirstlane(min(J + 1, nblocks - 1)) * (BLK * 4);
+            if constexpr (j == 0) film_row(film + layer * H);
+            f4 acc[2][2];
+#pragma unroll
+            for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+                for (int c = 0; c < 2; ++c) acc[rb][c] = an[rb][c];
+            static_for<NK>([&](auto kc) {
+                constexpr int k = decltype(kc)::value;
+                constexpr int q = k / 2, rb = k % 2;
+                h8 FH1 = FH, FL1 = FL;
+                if constexpr (k + 1 < NK && !(EXP & 4)) {
+                    FH1 = *(const h8*)(wb + (k + 1) * 512 + lane * 4);
+                    FL1 = *(const h8*)(wb + (k + 1) * 512 + 256 + lane * 4);
+                }
+                if constexpr (k == NK - 1) {
+                    if constexpr (j + 1 < NB2) film_row(film + layer * H + 32 * (j + 1));
+                    FH1 = *(const h8*)(nxt + lane * 4);
+                    FL1 = *(const h8*)(nxt + 256 + lane * 4);
+                }
+                if constexpr (k < PPW && !(EXP & 1)) {
+                    const int piece = wave + WAVES * k;
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(
+                        wrsrc, (__attribute__((address_space(3))) void*)(nxt + piece * 256), 16, lane * 16,
+                        soff + piece * 1024, 0, 0);
+                }
+                if constexpr (j == 0) {
+                    acc[rb][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(FL, NH[q].h(), acc[rb][0], 0, 0, 0);
+                    acc[rb][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(FL, NH[NQ + q].h(), acc[rb][1], 0, 0, 0);
+                    acc[rb][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(FH, NL[q].h(), acc[rb][0], 0, 0, 0);
+                    acc[rb][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(FH, NL[NQ + q].h(), acc[rb][1], 0, 0, 0);
+                    acc[rb][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(FH, NH[q].h(), acc[rb][0], 0, 0, 0);
+                    acc[rb][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(FH, NH[NQ + q].h(), acc[rb][1], 0, 0, 0);
+                    // group rb's copy of chunk q for slots 1.. (the other group's in the step beside)
+                    BH[rb * NQ + q] = NH[rb * NQ + q];
+                    BL[rb * NQ + q] = NL[rb * NQ + q];
+                    asm volatile("" : "+a"(BH[rb * NQ + q].v), "+a"(BL[rb * NQ + q].v));
+                } else {
+                    acc[rb][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(FL, BH[q].h(), acc[rb][0], 0, 0, 0);
+                    acc[rb][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(FL, BH[NQ + q].h(), acc[rb][1], 0, 0, 0);
+                    acc[rb][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(FH, BL[q].h(), acc[rb][0], 0, 0, 0);
+                    acc[rb][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(FH, BL[NQ + q].h(), acc[rb][1], 0, 0, 0);
+                    acc[rb][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(FH, BH[q].h(), acc[rb][0], 0, 0, 0);
+                    acc[rb][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(FH, BH[NQ + q].h(), acc[rb][1], 0, 0, 0);
+                }
+                if constexpr (k < NKS) {
+#pragma unroll
+                    for (int v = 16 * k / NKS; v < 16 * (k + 1) / NKS; ++v) {
+                        x[v] = (EXP & 2) ? prev[v] * me : hidden_sine<HWSIN>(prev[v] * me);
+                        asm volatile("" : "+v"(x[v]));
+                    }
+                }
+                // split: group c's values are chunk jp of the next layer (for j = 0, of this one)
+                constexpr int KE = NK >= 18 ? 16 : NKS - 1;
+                if constexpr (k == KE || k == (NK >= 18 ? 17 : KE)) {
+                    constexpr bool both = NK < 18;
+                    constexpr int c0 = (NK >= 18 && k == 17) ? 1 : 0;
+                    if (live) {
+#pragma unroll
+                        for (int c = c0; c < (both ? 2 : c0 + 1); ++c)
+                            split_chunk(x, c, NH[c * NQ + jp], NL[c * NQ + jp]);
+                        if (j > 0 && last) {
+#pragma unroll
+                            for (int c = c0; c < (both ? 2 : c0 + 1); ++c) {
+                                outsum(jp, c, 0);
+                                outsum(jp, c, 1);
+                            }
+                        }
+                    }
+                }
+                __builtin_amdgcn_sched_barrier(0);
+                FH = FH1;
+                FL = FL1;
+                if constexpr (k == NK - 2 && !(EXP & 1)) {
+                    __builtin_amdgcn_s_waitcnt(vm_lgkm0_imm(0));
+                    asm volatile("s_barrier" ::: "memory");
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            });
+#pragma unroll
+            for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+                for (int c = 0; c < 2; ++c)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) prev[8 * c + 4 * rb + r] = acc[rb][c][r];
+            ++J;
+        });
+        mprev = m;
+    }
+    // the last layer's last slot
+#pragma unroll
+    for (int v = 0; v < 16; ++v) x[v] = hidden_sine<HWSIN>(prev[v] * mprev);
+#pragma unroll
+    for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+        for (int oc = 0; oc < 4; ++oc) {
+            const f4 w = *(const f4*)(wos + oc * H + 32 * (NB2 - 1) + 16 * rb + 4 * g);
+#pragma unroll
+            for (int c = 0; c < 2; ++c)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) o[c][oc] = fmaf(w[r], x[8 * c + 4 * rb + r], o[c][oc]);
+        }
+
+    // ---- output layer (H -> c): reduce the 4 lane groups, bias, de-normalise; lane
+    // group g stores output g ----
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+        float ov[4];
+#pragma unroll
+        for (int oc = 0; oc < 4; ++oc) {
+            float sum = o[c][oc];
+            sum += __shfl_xor(sum, 16);
+            sum += __shfl_xor(sum, 32);
+            ov[oc] = oc < p.c ? sum + p.bout[oc] : 0.f;
+        }
+        const int64_t n = n0 + 16 * c;
+        if (n < p.N && g < p.c) {
+            float v = g == 0 ? ov[0] : g == 1 ? ov[1] : g == 2 ? ov[2] : ov[3];
+            if (p.ymax) {
+                const int64_t yi = n * p.ystride + g;
+                const float hi = p.ymax[yi], lo = p.ymin[yi];
+                v = (v + 1.0f) / 2.0f * (hi - lo) + lo;
+            }
+            p.out[(b * p.N + n) * p.c + g] = v;
+        }
+    }
+#ifdef CFD_STAMPS
+    if (stamped) CFD_STAMP(p.stamps, 5, (unsigned)blockIdx.y, 4);
+#endif
+}
+
+// SHAPE: the MFMA of the hidden layers, 32 (32x32x16) or 16 (16x16x32)
+template <int NB2, int EXP = 0, int HWSIN = 0, int SHAPE = 32>
+__global__ __launch_bounds__(256, 1) void siren_split32(SirenArgs p) {
+    if constexpr (SHAPE == 16) split16_body<NB2, EXP, HWSIN>(p);
+    else split32_body<NB2, EXP, HWSIN>(p);
+}
+
 namespace {
 
 template <int NB, int RING, int CG, int RB = 1, bool NOSYNC = false, bool PKSIN = true>
@@ -770,11 +1077,11 @@ void launch_nb(SirenArgs a, int b, hipStream_t st) {
 }
 }  // namespace
 
-template <int NB2, int EXP = 0, int HWSIN = 0>
+template <int NB2, int EXP = 0, int HWSIN = 0, int SHAPE = 32>
 void launch_split32(SirenArgs a, int b, hipStream_t st) {
     constexpr int H = NB2 * 32;
     const size_t lds = sizeof(float) * ((size_t)2 * 2 * NB2 * 512 + (size_t)(a.nh + 1) * H + 8 * H);
-    const void* fn = (const void*)siren_split32<NB2, EXP, HWSIN>;
+    const void* fn = (const void*)siren_split32<NB2, EXP, HWSIN, SHAPE>;
     CFD_REQUIRE((int64_t)a.nh * H * H * 4 < 0x7fffffffLL, CFD_EARG, "weight image beyond the 2 GiB buffer range");
     CFD_REQUIRE(lds <= 160 * 1024, CFD_EARG, "SIREN too deep for the split-f16 decoder's LDS staging");
     CFD_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -783,9 +1090,26 @@ void launch_split32(SirenArgs a, int b, hipStream_t st) {
     for (int64_t b0 = 0; b0 < b; b0 += 65535) {
         a.b0 = b0;
         const int nb = (int)std::min<int64_t>(65535, b - b0);
-        hipLaunchKernelGGL((siren_split32<NB2, EXP, HWSIN>), dim3((unsigned)tiles, nb), dim3(256), lds, st, a);
+        hipLaunchKernelGGL((siren_split32<NB2, EXP, HWSIN, SHAPE>), dim3((unsigned)tiles, nb), dim3(256), lds, st, a);
         check_launch("siren_split32");
     }
+}
+
+// the hidden layers' MFMA shape per width (32: 32x32x16, 16: 16x16x32), chosen by
+// wall time.  A development build takes one shape for every
+// width: make VARIANT=shape16 VFLAGS=-DCFD_SPLIT32_SHAPE=16 (or 32), loaded with CFD_LIB.
+#ifdef CFD_SPLIT32_SHAPE
+constexpr int SHAPE_64 = CFD_SPLIT32_SHAPE, SHAPE_128 = CFD_SPLIT32_SHAPE, SHAPE_256 = CFD_SPLIT32_SHAPE,
+              SHAPE_384 = CFD_SPLIT32_SHAPE;
+#else
+constexpr int SHAPE_64 = 32, SHAPE_128 = 16, SHAPE_256 = 16, SHAPE_384 = 16;
+#endif
+static_assert((SHAPE_64 == 16 || SHAPE_64 == 32) && (SHAPE_384 == 16 || SHAPE_384 == 32), "the shape define takes 16 or 32");
+
+template <int NB2, int SHAPE>
+void launch_split32_shape(SirenArgs a, int b, hipStream_t st) {
+    a.wimg = SHAPE == 16 ? a.wimg_rev16 : a.wimg_rev;
+    launch_split32<NB2, 0, 4, SHAPE>(a, b, st);
 }
 
 bool siren_split32_supported(int H, int nh) {
@@ -800,13 +1124,12 @@ bool siren_split32_supported(int H, int nh) {
 // revolutions) stay in the sine probe (cfd_sine_probe) and the K7s/K9d kernels;
 // their full decoder instantiations were removed in round 3.
 void launch_siren_split32(int H, SirenArgs a, int b, hipStream_t st) {
-    CFD_REQUIRE(a.wimg_rev && a.wrev, CFD_EARG, "split32 revolution image not set");
-    a.wimg = a.wimg_rev;
+    CFD_REQUIRE(a.wimg_rev && a.wimg_rev16 && a.wrev, CFD_EARG, "split32 revolution images not set");
     switch (H) {
-        case 64: return launch_split32<2, 0, 4>(a, b, st);
-        case 128: return launch_split32<4, 0, 4>(a, b, st);
-        case 256: return launch_split32<8, 0, 4>(a, b, st);
-        case 384: return launch_split32<12, 0, 4>(a, b, st);
+        case 64: return launch_split32_shape<2, SHAPE_64>(a, b, st);
+        case 128: return launch_split32_shape<4, SHAPE_128>(a, b, st);
+        case 256: return launch_split32_shape<8, SHAPE_256>(a, b, st);
+        case 384: return launch_split32_shape<12, SHAPE_384>(a, b, st);
         default: throw Error{CFD_EARG, "32x32 split-f16 SIREN needs hidden_features in {64, 128, 256, 384}"};
     }
 }

@@ -20,68 +20,14 @@
 // traffic is the value column's pre-activation, which the tangent columns of its
 // group read with one DPP quad-permute move (no LDS); each lane then runs one range
 // reduction and one polynomial: the sine in the value column, the cosine in the
-// tangent columns (sincos_role below, bit for bit sin_cw / cos_cw of common.hpp).
+// tangent columns (sincos_role, siren_jac.hpp: bit for bit sin_cw / cos_cw of common.hpp).
 // Activations and tangents never leave registers; X[NB][4] / acc[NB] are
 // siren_fused's, so is the register budget.
 #include <algorithm>
 
-#include "siren.hpp"
+#include "siren_jac.hpp"
 
 namespace cfd {
-
-struct SirenJacArgs {
-    const float* w0;      // (H, d)
-    const float* wimg;    // hidden weight image (as SirenArgs)
-    const float* wout;    // (c, H)
-    const float* bout;    // (c)
-    const float* film;    // (b, nh+1, H)
-    const float* coords;  // (N, d)
-    const float* xmax;
-    const float* xmin;
-    const float* ymax;
-    const float* ymin;
-    float* out;           // (b, N, c) or null
-    float* jac;           // (b, N, c, d)
-    int64_t N;
-    int64_t ystride;
-    int64_t b0;
-    int b;                // latent rows of the call (index assertions)
-    int d, c, nh;
-    float w0f;
-};
-
-// sin(x) where value is set, cos(x) elsewhere, from one reduction: sin_cw reduces by
-// q pi and cos_cw by an odd q' pi/2 with a split of pi/2 whose every term is exactly
-// half of sin_cw's, so fmaf(2q, c/2, x) == fmaf(q, c, x) bit for bit and both are
-// "x - qq * (pi/2 split)" with qq = 2q (sine) or q' (cosine); the polynomial is
-// shared.  sin: negate for odd q (qq & 2); cos: negate unless qq & 2.
-__device__ __forceinline__ float sincos_role(float x, bool value) {
-    const float t = fmaf(x, 0.318309886183790671538f, value ? 0.0f : -0.5f);
-    const float qq = fmaf(2.0f, rintf(t), value ? 0.0f : 1.0f);
-    float r = fmaf(qq, -1.5703125f, x);
-    r = fmaf(qq, -0.00048351287841796875f, r);
-    r = fmaf(qq, -3.13855707645416259765625e-07f, r);
-    r = fmaf(qq, -6.077100628276710381e-11f, r);
-    const float s = r * r;
-    float u = 2.6083159809786593541503e-06f;
-    u = fmaf(u, s, -0.0001981069071916863322258f);
-    u = fmaf(u, s, 0.00833307858556509017944336f);
-    u = fmaf(u, s, -0.166666597127914428710938f);
-    const float y = fmaf(s, u * r, r);
-    const bool neg = (((unsigned)(int)qq & 2u) != 0u) == value;
-    const float v = __uint_as_float(__float_as_uint(y) ^ (neg ? (1u << 31) : 0u));
-    const float xr = x * 0.159154943091895335768f;
-    const float hw = value ? __builtin_amdgcn_sinf(xr) : __builtin_amdgcn_cosf(xr);
-    return fabsf(x) < 39000.0f ? v : hw;
-}
-
-// the value column's copy of v within each group of RS columns (lanes of a group
-// are adjacent and groups never straddle a quad): DPP quad_perm, no LDS
-template <int RS>
-__device__ __forceinline__ float group_value(float v) {
-    constexpr int ctrl = RS == 4 ? 0x00 /* quad_perm [0,0,0,0] */ : 0xA0 /* quad_perm [0,0,2,2] */;
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), ctrl, 0xF, 0xF, false));
-}
 
 template <int NB, int RS, int WAVES>
 __global__ __launch_bounds__(64 * WAVES, NB <= 24 ? 2 : 1) void siren_jac_fused(SirenJacArgs p) {

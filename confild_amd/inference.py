@@ -47,6 +47,13 @@ reference-preserving defaults:
                                launch per chunk, which leaves the files above as they are: hessian
                                (..., c, d, d), laplacian (..., c), grad_divergence (..., d).  laplacian
                                alone runs the diagonal form)
+  derived_compute: f32        (f32 | split_f16: the arithmetic of the Jacobian launch behind jacobian |
+                               vorticity | divergence | q_criterion.  f32: the exact fp32 MFMA chain;
+                               split_f16: the same chain on the f16 matrix pipes with fp32-level
+                               accuracy (decode_jacobian(compute="split_f16")), for CNF widths
+                               hidden_features 32*{1,2,3,4,6,8,12}, num_hidden_layers >= 1, dims <= 3 --
+                               any other value or width is a ValueError before sampling starts.  The
+                               fields and the Hessian names do not depend on it)
   derived_velocity_channels:  (which d output channels are the velocity, default the first d)
 Known deviation (fixed on purpose): ``channel_mult`` from the YAML IS passed to
 create_model (the reference reads but drops it, inference.py:38-44, so its own
@@ -132,6 +139,22 @@ def derived_names(inp):
     return names
 
 
+def derived_compute(inp):
+    """The ``derived_compute`` YAML key: "f32" (default) or "split_f16".  split_f16 is
+    checked here against the widths in the CNF case file (no model is loaded), so a
+    run the kernel would refuse stops before sampling."""
+    from .nf_networks import JACOBIAN_COMPUTE, jacobian_split_refusal
+    mode = str(getattr(inp, "derived_compute", None) or "f32")
+    if mode not in JACOBIAN_COMPUTE:
+        raise ValueError(f"derived_compute must be one of {list(JACOBIAN_COMPUTE)}, got {mode!r}")
+    if mode == "split_f16":
+        cnf = basic_input(inp.cnf_case_file_path)
+        why = jacobian_split_refusal(int(cnf.dims), int(cnf.NF["num_hidden_layers"]), int(cnf.NF["hidden_features"]))
+        if why:
+            raise ValueError(f"derived_compute: split_f16 does not take this CNF: {why}")
+    return mode
+
+
 def derived_quantity(name, jac, velocity_channels=None, hess=None, diag=False):
     """One ``derived`` quantity of a Jacobian (..., c, d) or, for HESSIAN_DERIVED, of a
     Hessian (..., c, d, d) (``diag``: its diagonal form (..., c, d), enough for laplacian)."""
@@ -194,6 +217,7 @@ def run(yaml_path: str):
     if device.type != "cuda":
         raise _lib.CfdError("confild_amd.inference needs a GPU")
     inp = basic_input(yaml_path)
+    jcompute = derived_compute(inp)                          # raises before any model is built
     seed = int(getattr(inp, "seed", 42))
     torch.manual_seed(seed)
     np.random.seed(seed)
@@ -277,10 +301,10 @@ def run(yaml_path: str):
     for a in range(s, e, rows):
         chunk = lat[a:min(e, a + rows)]
         # the fields are the plain decode's whether or not `derived` is set (the Jacobian
-        # launch is always the exact fp32 chain; its values are not the ones saved)
+        # launch's values are not the ones saved, whatever derived_compute it runs)
         fields.append(cnf.infer(coord, chunk))
         if jnames:
-            jac = cnf.infer_jacobian(coord, chunk)[1]
+            jac = cnf.infer_jacobian(coord, chunk, compute=jcompute)[1]
             for n in jnames:
                 extra[n].append(derived_quantity(n, jac, vch))
         if hnames:

@@ -55,6 +55,32 @@ def latent_grad_flops(d, L, c, nh, H, rows, points):
     return {"forward": fwd, "backward": bwd}
 
 
+JACOBIAN_COMPUTE = ("f32", "split_f16")                 # decode_jacobian(compute=...)
+JACOBIAN_SPLIT_WIDTHS = tuple(32 * k for k in (1, 2, 3, 4, 6, 8, 12))
+
+
+def jacobian_split_refusal(d, nh, H):
+    """Why decode_jacobian(compute="split_f16") refuses a network of ``d`` coordinate
+    features, ``nh`` hidden layers of width ``H`` (the rule of
+    cfd_siren_forward_jacobian_split, no library call), or None when it runs."""
+    if not 1 <= d <= 3:
+        return f"in_coord_features must be 1..3, got {d} (the 1 + d chains of a point share 4 MFMA columns)"
+    if nh < 1:
+        return f"num_hidden_layers must be >= 1, got {nh} (no hidden product to run on f16 MFMA)"
+    if H % 32:
+        return f"hidden_features must be a multiple of 32, got {H} (32-feature K-chunks of the f16 MFMA)"
+    if H not in JACOBIAN_SPLIT_WIDTHS:
+        return f"hidden_features must be one of {list(JACOBIAN_SPLIT_WIDTHS)}, got {H}"
+    if 4 * (2 * (H // 16) * 256 + (nh + 1) * H + 4 * H) > 160 * 1024:
+        return f"{nh} hidden layers of width {H} are too deep for the LDS staging (160 KiB)"
+    return None
+
+
+def jacobian_split_supported(d, nh, H):
+    """True when decode_jacobian(compute="split_f16") takes these widths."""
+    return jacobian_split_refusal(d, nh, H) is None
+
+
 class SIRENAutodecoder_film(nn.Module):
     """Constructor as nf_networks.py:447-478 (sine nonlinearity, no premap)."""
 
@@ -245,12 +271,18 @@ class SIRENAutodecoder_film(nn.Module):
         return out.reshape((b,) + spatial + (c,))
 
     # -- value and coordinate Jacobian (K13: cfd_siren_forward_jacobian) ------------
-    def decode_jacobian(self, coords, latents, x_normalizer=None, y_normalizer=None):
+    def decode_jacobian(self, coords, latents, x_normalizer=None, y_normalizer=None, compute=None):
         """decode() together with its exact spatial derivatives, one fused launch:
         returns (out (b, *spatial, c), jac (b, *spatial, c, d)) with jac[..., o, k] =
         d out[..., o] / d coords[..., k], both in physical units (the chain rule through
-        the normalisers is applied).  Broadcasting as decode().  Always the exact fp32
-        chain, whatever set_compute chose.  Only '-11' normalisers (fused)."""
+        the normalisers is applied).  Broadcasting as decode().  Only '-11' normalisers
+        (fused).  ``compute``: None or "f32", the exact fp32 chain (K13), whatever
+        set_compute chose; "split_f16", the same chain on the f16 matrix pipes with
+        fp32-level accuracy (K13s, cfd_siren_forward_jacobian_split), for the widths
+        jacobian_split_supported() names -- any other width is a CfdError, never a
+        fall-back."""
+        if compute not in (None,) + JACOBIAN_COMPUTE:
+            raise ValueError(f"compute must be None or one of {list(JACOBIAN_COMPUTE)}, got {compute!r}")
         d, L, c = self.in_coord_features, self.in_latent_features, self.out_features
         dev = latents.device
         if dev.type != "cuda":
@@ -268,10 +300,10 @@ class SIRENAutodecoder_film(nn.Module):
         ws = torch.empty(max(nbytes.value, 16), dtype=torch.uint8, device=dev)
         out = torch.empty((b, N, c), dtype=torch.float32, device=dev)
         jac = torch.empty((b, N, c, d), dtype=torch.float32, device=dev)
-        _lib.check(lib.cfd_siren_forward_jacobian(h, _lib.ptr(cf), N, _lib.ptr(lat), b, _lib.ptr(xmax),
-                                                  _lib.ptr(xmin), _lib.ptr(ymax), _lib.ptr(ymin), ystride,
-                                                  _lib.ptr(out), _lib.ptr(jac), _lib.ptr(ws), ws.numel(),
-                                                  _lib.stream_of(dev)), "cfd_siren_forward_jacobian")
+        name = "cfd_siren_forward_jacobian_split" if compute == "split_f16" else "cfd_siren_forward_jacobian"
+        _lib.check(getattr(lib, name)(h, _lib.ptr(cf), N, _lib.ptr(lat), b, _lib.ptr(xmax), _lib.ptr(xmin),
+                                      _lib.ptr(ymax), _lib.ptr(ymin), ystride, _lib.ptr(out), _lib.ptr(jac),
+                                      _lib.ptr(ws), ws.numel(), _lib.stream_of(dev)), name)
         return out.reshape((b,) + spatial + (c,)), jac.reshape((b,) + spatial + (c, d))
 
     # -- value, Jacobian and coordinate Hessian (K14: cfd_siren_forward_hessian) ------

@@ -81,16 +81,17 @@ class trainer:
             return self.nf.decode(coord, latents.reshape(latents.shape[0], -1)[:, None],
                                   self.in_normalizer, self.out_normalizer)
 
-    def infer_jacobian(self, coord, latents):
+    def infer_jacobian(self, coord, latents, compute=None):
         """infer() with the fields' exact spatial derivatives: (fields (b, N, c), jac
         (b, N, c, d)) (or (b, h, w, c) / (b, h, w, c, d) for grid coordinates), jac =
-        d fields / d coord in physical units (SIRENAutodecoder_film.decode_jacobian)."""
+        d fields / d coord in physical units (SIRENAutodecoder_film.decode_jacobian,
+        which ``compute`` -- None, "f32" or "split_f16" -- is passed to)."""
         coord = coord if coord is not None else self.train_coord
         if coord is None:
             raise ValueError("no query coordinates: pass coord (infer_mode=True has no training points)")
         with torch.no_grad():
             return self.nf.decode_jacobian(coord, latents.reshape(latents.shape[0], -1)[:, None],
-                                           self.in_normalizer, self.out_normalizer)
+                                           self.in_normalizer, self.out_normalizer, compute=compute)
 
     def infer_hessian(self, coord, latents, diag=False):
         """infer_jacobian() with the exact second derivatives: (fields, jac, hess), hess

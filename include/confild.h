@@ -388,6 +388,23 @@ int  cfd_siren_forward_jacobian(cfd_siren* h, const float* coords, int64_t N, co
                                 const float* ymax, const float* ymin, int64_t y_stride,
                                 float* out, float* jac,
                                 void* workspace, size_t ws_bytes, void* stream);
+/* cfd_siren_forward_jacobian on the f16 matrix pipes with fp32-level accuracy
+ * (csrc/siren_jac_split.hip, K13s): every hidden product as three
+ * v_mfma_f32_16x16x32_f16 on hi/lo f16 halves (CFD_SIREN_SPLIT_F16's arithmetic).
+ * Each tangent column is split at a power-of-two scale of its own, taken per layer
+ * from the column's largest magnitude and undone exactly at the head, so no finite
+ * tangent overflows an f16 half and scaling the coordinates by a power of two scales
+ * jac by exactly its inverse.  Same parameters, normaliser forms, workspace
+ * (cfd_siren_jacobian_workspace_bytes), NULL out and invariances as
+ * cfd_siren_forward_jacobian; not selected by cfd_siren_set_compute.  Besides that
+ * entry's errors, CFD_EARG before any launch unless hidden_features is
+ * 32*{1,2,3,4,6,8,12}, num_hidden_layers >= 1, in_coord_features <= 3 and the LDS
+ * staging (2 weight blocks + the FiLM rows) is within 160 KiB. */
+int  cfd_siren_forward_jacobian_split(cfd_siren* h, const float* coords, int64_t N, const float* latents, int b,
+                                      const float* xmax, const float* xmin,
+                                      const float* ymax, const float* ymin, int64_t y_stride,
+                                      float* out, float* jac,
+                                      void* workspace, size_t ws_bytes, void* stream);
 /* The same with the second derivatives, one fused launch (csrc/siren_hess.hip):
  * hess (b, N, c, d, d), hess[b, n, o, k, l] = d2 out[b, n, o] / d coords[n, k]
  * d coords[n, l] in physical units (the coordinate scales of both axes and

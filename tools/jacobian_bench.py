@@ -1,23 +1,28 @@
-"""Time the fused value-and-Jacobian decode (K13, cfd_siren_forward_jacobian) against
-the plain decode, and check that the change left every existing kernel alone.
+"""Time the fused value-and-Jacobian decodes (K13, cfd_siren_forward_jacobian; K13s,
+cfd_siren_forward_jacobian_split) against the plain decode, and check that the change
+left every existing kernel alone.
 
     python tools/jacobian_bench.py [--parent libconfild_hip_parent.so] [--ratios FILE]
-                                   [--out profiles/siren_jacobian.json]
+                                   [--out profiles/siren_jacobian_split.json]
 
 Timing (in this process): per shape (d, L, c, nh, H), the same N = 65,536 points
 and 8 latent rows through
   decode/f32        SIRENAutodecoder_film.decode, exact fp32 MFMA chain
   decode/split_f16  the same decode in the default split-f16 mode (context)
-  jacobian          decode_jacobian (always the exact fp32 chain)
-warm runs first, then `--rounds` rounds interleaving the three, each `--iters`
+  jacobian          decode_jacobian (the exact fp32 chain, K13)
+  jacobian/split_f16  decode_jacobian(compute="split_f16") (K13s)
+warm runs first, then `--rounds` rounds interleaving the four, each `--iters`
 back-to-back calls between two device events.  The model is (1 + d) x the f32
-decode (the chains of a point share an MFMA; 4 x with the idle column at d = 2).
+decode (the chains of a point share an MFMA; 4 x with the idle column at d = 2);
+for the split form, the RS = 4 MFMA columns a point takes against the split decode's
+one.  (profiles/siren_jacobian.json is the three-form record of K13's own change.)
 
 --parent: a build of the parent commit under confild_amd/lib.  Runs tools/libdiff.py
 (every case's output hash, parent against this build) and `python bench.py`
 alternating between the two libraries (CFD_LIB), `--bench-rounds` runs each.
---ratios: the JSON lines tests/test_gpu_siren_jacobian.py prints (pytest -s), kept
-as the measured error ratios.
+--ratios: the JSON lines tests/test_gpu_siren_jacobian.py or
+tests/test_gpu_siren_jacobian_split.py print (pytest -s), kept as the measured error
+ratios.
 """
 from __future__ import annotations
 
@@ -55,7 +60,8 @@ def time_shape(dims, rounds, iters):
         return nf.decode(coords, lat, xn, yn)
 
     runs = {"decode/f32": lambda: decode("f32"), "decode/split_f16": lambda: decode("split_f16"),
-            "jacobian": lambda: nf.decode_jacobian(coords, lat, xn, yn)}
+            "jacobian": lambda: nf.decode_jacobian(coords, lat, xn, yn),
+            "jacobian/split_f16": lambda: nf.decode_jacobian(coords, lat, xn, yn, compute="split_f16")}
     for fn in runs.values():          # warm: code objects, handle, normaliser cache
         for _ in range(3):
             fn()
@@ -76,10 +82,18 @@ def time_shape(dims, rounds, iters):
     ratio = best["jacobian"] / best["decode/f32"]
     # hidden-layer FLOP of the launch as the algorithm needs them: (1 + d) chains
     flops = 2.0 * nh * H * H * (1 + d) * N * ROWS
+    split = "jacobian/split_f16"
+    columns = 2 if d == 1 else 4        # MFMA columns per point (RS) against the split decode's one
     return {"dims": list(dims), "N": N, "rows": ROWS, "ms_per_call": ms, "best_ms": best,
             "jacobian_over_decode_f32": ratio, "model": model, "ratio_over_model": ratio / model,
             "jacobian_over_decode_split_f16": best["jacobian"] / best["decode/split_f16"],
-            "jacobian_hidden_tflops": flops / (best["jacobian"] * 1e-3) / 1e12}
+            "jacobian_hidden_tflops": flops / (best["jacobian"] * 1e-3) / 1e12,
+            "split_slowest_ms": max(ms[split]), "jacobian_fastest_ms": best["jacobian"],
+            "split_slowest_below_jacobian_fastest": max(ms[split]) < best["jacobian"],
+            "jacobian_over_split": best["jacobian"] / best[split],
+            "split_over_decode_split_f16": best[split] / best["decode/split_f16"], "column_model": columns,
+            "split_ratio_over_column_model": best[split] / best["decode/split_f16"] / columns,
+            "split_hidden_tflops": flops / (best[split] * 1e-3) / 1e12}
 
 
 def bench_headline(lib, steps, warmup):
@@ -126,21 +140,23 @@ def main():
     ap.add_argument("--bench-steps", type=int, default=2)
     ap.add_argument("--bench-warmup", type=int, default=1)
     ap.add_argument("--ratios", default=None)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "siren_jacobian.json"))
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "siren_jacobian_split.json"))
     a = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("tools/jacobian_bench.py measures on the GPU; no HIP device is visible")
-    doc = {"what": "decode_jacobian (fused value + coordinate Jacobian, exact fp32 MFMA chain) against decode; "
-                   f"N = {N} points, {ROWS} latent rows, synthetic weights; ms per call from device events around "
-                   f"{a.iters} back-to-back calls, the three interleaved for {a.rounds} rounds after warm runs; "
-                   "best_ms = fastest round",
+    doc = {"what": "decode_jacobian (fused value + coordinate Jacobian) on the exact fp32 MFMA chain and on the "
+                   f"split-f16 chain, against decode; N = {N} points, {ROWS} latent rows, synthetic weights; ms per "
+                   f"call from device events around {a.iters} back-to-back calls, the four interleaved for "
+                   f"{a.rounds} rounds after warm runs; best_ms = fastest round",
            "timing": []}
     for dims in SHAPES:
         one = time_shape(dims, a.rounds, a.iters)
         doc["timing"].append(one)
-        print(json.dumps({k: one[k] for k in ("dims", "best_ms", "jacobian_over_decode_f32", "model",
-                                              "ratio_over_model")}), flush=True)
+        print(json.dumps({k: one[k] for k in ("dims", "ms_per_call", "jacobian_over_decode_f32", "model",
+                                              "ratio_over_model", "jacobian_over_split",
+                                              "split_slowest_below_jacobian_fastest",
+                                              "split_over_decode_split_f16")}), flush=True)
     if a.ratios:
         rows = []
         for ln in open(a.ratios):
@@ -148,7 +164,7 @@ def main():
                 rows.append(json.loads(ln[ln.index("{"):].strip()))
         doc["error_ratios"] = {"what": "|jac - J64| over max(e32, 1e-7 |J64|max), max and mean; J64: autograd through "
                                        "the CPU oracle in fp64, e32: the CPU fp32 autograd's error against it "
-                                       "(tests/test_gpu_siren_jacobian.py)", "cases": rows,
+                                       "(the Jacobian tests)", "cases": rows,
                                "largest": max([max(r["ratio_max"], r["ratio_mean"]) for r in rows], default=None)}
     if a.parent:
         doc["existing_kernels"] = untouched(a.parent, a.bench_rounds, a.bench_steps, a.bench_warmup)

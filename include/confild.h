@@ -500,8 +500,14 @@ int  cfd_siren_dense_set_form(cfd_siren* h, int bwd_form, int compute_form);
  *                 and reference shapes (torch's .grad accumulation);          *
  *   grad_latents  (N_samples, L): the batch's rows;                           *
  *   sse           (1) sum of squared errors of this call.                     *
- * fp32 throughout (fp32 MFMA tape chain, fp32 MFMA weight-gradient products   *
- * over the (row, coordinate) pairs); deterministic.                           */
+ * The tape chain (forward with tape, backward to every delta) follows the      *
+ * handle's compute mode: in CFD_SIREN_SPLIT_F16 at H = 128 / 256 / 384 with at *
+ * least one hidden layer and fewer than 32,768 (row, coordinate) pairs in the  *
+ * call it is K9t, the split-f16 tape (fp32-level error); at every other width, *
+ * from 32,768 pairs on, and always under CFD_SIREN_F32, the fp32 MFMA tape.    *
+ * The weight-gradient products over the pairs, the column sums and the latent  *
+ * gradient are fp32 MFMA / fp32 sums in every mode (the activations recomputed *
+ * from the tape the chain wrote).  Deterministic: fixed slicing and order.     */
 int  cfd_siren_train_workspace_bytes(const cfd_siren* h, int64_t N, int R, size_t* bytes);
 int  cfd_siren_train_grad(cfd_siren* h, const float* coords, int64_t N, const float* latents,
                           const int64_t* rows, int R, const float* target, float scale,

@@ -138,6 +138,15 @@ _SIGS = {
                                          C.c_size_t, C.c_void_p]),
     "cfd_siren_tape_vjp": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p,
                                      C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "cfd_siren_jtape_workspace_bytes": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_size_t)]),
+    "cfd_siren_jtape_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_size_t, C.c_void_p]),
+    "cfd_siren_jtape_vjp": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p,
+                                      C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "cfd_dps_residual_linear": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                          C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "cfd_siren_dense_plan": (C.c_int, [C.POINTER(SirenCfg), C.c_int64, C.c_int, C.c_size_t, C.c_int, C.c_int,
                                        C.POINTER(C.c_size_t), C.POINTER(C.c_int64), C.POINTER(C.c_int)]),
     "cfd_siren_dense_workspace_bytes": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_size_t,

@@ -235,6 +235,103 @@ __global__ __launch_bounds__(256) void dps_residual_kernel(const float* __restri
     }
 }
 
+// Linear sensor stencils on the value and the coordinate Jacobian (K15's residual):
+//   A[r, s, m] = sum_o wv[s, m, o] out[r, s, o] + sum_{o,k} wj[s, m, o, k] jac[r, s, o, k]
+// per sample b (rows_per_sample rows): norm_b = ||y - A||_2 (float64 sum, the order of
+// dps_residual_kernel), g_out = wv^T (-(y - A) / norm_b), g_jac = wj^T (-(y - A) / norm_b);
+// zero gradients where the norm is 0.  One thread per (row, sensor); A is formed by
+// the same code in both passes, so the gradient uses the residual the norm summed.
+struct DpsLinearArgs {
+    const float* y;       // (rows_per_sample | R, Ns, M)
+    const float* out;     // (R, Ns, c)
+    const float* jac;     // (R, Ns, c, d) or null
+    const float* wv;      // (1 | Ns, M, c) or null
+    const float* wj;      // (1 | Ns, M, c, d) or null
+    float* g_out;         // (R, Ns, c) or null
+    float* g_jac;         // (R, Ns, c, d) or null
+    float* norm;          // (B)
+    float* A;             // (R, Ns, M) or null
+    int64_t wv_stride, wj_stride;   // per sensor: 0 (shared) or M c / M c d
+    int y_per_sample, Ns, M, c, d, rows;
+};
+
+__device__ __forceinline__ float dps_linear_A(const DpsLinearArgs& p, const float* o, const float* j, int s, int m) {
+    float a = 0.f;
+    if (p.wv) {
+        const float* w = p.wv + s * p.wv_stride + (int64_t)m * p.c;
+        for (int q = 0; q < p.c; ++q) a = fmaf(w[q], o[q], a);
+    }
+    if (p.wj) {
+        const float* w = p.wj + s * p.wj_stride + (int64_t)m * p.c * p.d;
+        for (int q = 0; q < p.c * p.d; ++q) a = fmaf(w[q], j[q], a);
+    }
+    return a;
+}
+
+__global__ __launch_bounds__(256) void dps_residual_linear(DpsLinearArgs p) {
+    const int64_t b = blockIdx.x;
+    const int np = p.rows * p.Ns;   // (row, sensor) pairs of the sample
+    const int cd = p.c * p.d;
+    double sum = 0.0;
+    for (int i = threadIdx.x; i < np; i += blockDim.x) {
+        const int64_t pr = b * np + i;
+        const int s = i % p.Ns;
+        const float* yb = p.y + (p.y_per_sample ? pr : (int64_t)i) * p.M;
+        const float* o = p.out + pr * p.c;
+        const float* j = p.jac ? p.jac + pr * cd : nullptr;
+        for (int m = 0; m < p.M; ++m) {
+            const float a = dps_linear_A(p, o, j, s, m);
+            if (p.A) p.A[pr * p.M + m] = a;
+            const float r = yb[m] - a;
+            sum += (double)r * r;
+        }
+    }
+    __shared__ double red[256];
+    red[threadIdx.x] = sum;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+        __syncthreads();
+    }
+    const float nb = (float)sqrt(red[0]);
+    if (threadIdx.x == 0) p.norm[b] = nb;
+    for (int i = threadIdx.x; i < np; i += blockDim.x) {
+        const int64_t pr = b * np + i;
+        const int s = i % p.Ns;
+        const float* yb = p.y + (p.y_per_sample ? pr : (int64_t)i) * p.M;
+        const float* o = p.out + pr * p.c;
+        const float* j = p.jac ? p.jac + pr * cd : nullptr;
+        float go[4] = {0.f, 0.f, 0.f, 0.f};
+        float gj[12] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        for (int m = 0; m < p.M; ++m) {
+            const float r = yb[m] - dps_linear_A(p, o, j, s, m);
+            const float gm = nb > 0.f ? -(r / nb) : 0.f;
+            if (p.wv) {
+                const float* w = p.wv + s * p.wv_stride + (int64_t)m * p.c;
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+                    if (q < p.c) go[q] = fmaf(w[q], gm, go[q]);
+            }
+            if (p.wj) {
+                const float* w = p.wj + s * p.wj_stride + (int64_t)m * cd;
+#pragma unroll
+                for (int q = 0; q < 12; ++q)
+                    if (q < cd) gj[q] = fmaf(w[q], gm, gj[q]);
+            }
+        }
+        if (p.g_out) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                if (q < p.c) p.g_out[pr * p.c + q] = go[q];
+        }
+        if (p.g_jac) {
+#pragma unroll
+            for (int q = 0; q < 12; ++q)
+                if (q < cd) p.g_jac[pr * cd + q] = gj[q];
+        }
+    }
+}
+
 // g_z -> (d_eps, g_direct) through Case4Operator._unnorm (measurements.py:219-220),
 // clamp(-1, 1) (posterior_mean_variance.py:40-45; gradient passes on the closed
 // interval) and x0 = sra * x - srm1 * eps (:120-123)
@@ -625,6 +722,42 @@ extern "C" int cfd_dps_residual(const float* y, int64_t y_batch_stride, const fl
         hipLaunchKernelGGL(cfd::dps_residual_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, y, y_batch_stride, A,
                            g_A, norm, n_per_sample);
         cfd::check_launch("dps_residual_kernel");
+    });
+}
+
+extern "C" int cfd_dps_residual_linear(const float* y, int y_per_sample, const float* out, const float* jac,
+                                       const float* wv, int wv_per_sensor, const float* wj, int wj_per_sensor,
+                                       float* g_out, float* g_jac, float* norm, float* A, int64_t Ns, int M, int c,
+                                       int d, int rows_per_sample, int B, void* stream) {
+    return cfd::guard([&] {
+        CFD_REQUIRE(y && out && norm && (wv || wj), CFD_EARG, "null argument (at least one weight set is required)");
+        CFD_REQUIRE((wv == nullptr) == (g_out == nullptr), CFD_EARG, "wv and g_out must both be set or both NULL");
+        CFD_REQUIRE((wj == nullptr) == (g_jac == nullptr) && (!wj || jac), CFD_EARG,
+                    "wj, jac and g_jac must all be set or wj and g_jac both NULL");
+        CFD_REQUIRE(Ns >= 1 && Ns <= (1 << 20) && M >= 1 && c >= 1 && c <= 4 && d >= 1 && d <= 3 &&
+                        rows_per_sample >= 1 && B >= 1,
+                    CFD_EARG, "bad shape (c <= 4, d <= 3)");
+        CFD_REQUIRE((int64_t)rows_per_sample * Ns <= 0x7fffffff, CFD_EARG, "too many (row, sensor) pairs per sample");
+        cfd::DpsLinearArgs p{};
+        p.y = y;
+        p.out = out;
+        p.jac = jac;
+        p.wv = wv;
+        p.wj = wj;
+        p.g_out = g_out;
+        p.g_jac = g_jac;
+        p.norm = norm;
+        p.A = A;
+        p.wv_stride = wv_per_sensor ? (int64_t)M * c : 0;
+        p.wj_stride = wj_per_sensor ? (int64_t)M * c * d : 0;
+        p.y_per_sample = y_per_sample;
+        p.Ns = (int)Ns;
+        p.M = M;
+        p.c = c;
+        p.d = d;
+        p.rows = rows_per_sample;
+        hipLaunchKernelGGL(cfd::dps_residual_linear, dim3(B), dim3(256), 0, (hipStream_t)stream, p);
+        cfd::check_launch("dps_residual_linear");
     });
 }
 

@@ -1523,6 +1523,33 @@ void launch_tape(const cfd_siren* h, const cfd::SirenTapeArgs& a, bool bwd, hipS
 
 }  // namespace
 
+namespace cfd {
+
+// g_z (R, L) = (sum over sensors of delta (R, Ns, nl, H)) . V in a fixed order: one
+// fp32 MFMA GEMM through D (R nl H floats, then the GEMM's split-K partials), or
+// siren_latent_grad where the GEMM has no form for the shape
+void latent_grad_from_delta(const cfd_siren* h, const float* delta, float* D, int64_t Ns, int R, float* g_latents,
+                            hipStream_t st) {
+    const int nh = h->cfg.num_hidden_layers, H = h->cfg.hidden_features, L = h->cfg.in_latent_features;
+    const int64_t nf = (int64_t)(nh + 1) * H;
+    if (L % 4 == 0 && nf % 16 == 0) {
+        hipLaunchKernelGGL(sensor_sum_kernel, dim3((unsigned)ceil_div(R * nf, 256)), dim3(256), 0, st, delta, D,
+                           (int)Ns, nf, (int64_t)R);
+        check_launch("sensor_sum_kernel");
+        launch_gemm_f32(false, D, (int)nf, h->V, L, nullptr, g_latents, L, R, L, (int)nf, st, D + R * nf);
+    } else {
+        const size_t lds = sizeof(float) * (size_t)(nh + 1) * H;
+        CFD_REQUIRE(lds <= 160 * 1024, CFD_EARG, "SIREN too deep for the latent-gradient reduction");
+        CFD_HIP(hipFuncSetAttribute((const void*)siren_latent_grad, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)lds));
+        hipLaunchKernelGGL(siren_latent_grad, dim3(R), dim3(256), lds, st, delta, h->V, g_latents, (int)Ns, nh + 1, H,
+                           L);
+        check_launch("siren_latent_grad");
+    }
+}
+
+}  // namespace cfd
+
 extern "C" int cfd_siren_vjp_workspace_bytes(const cfd_siren* h, int64_t Ns, int R, size_t* bytes) {
     return cfd::guard([&] {
         CFD_REQUIRE(h && bytes && Ns >= 0 && R >= 0, CFD_EARG, "bad argument");
@@ -1572,7 +1599,7 @@ extern "C" int cfd_siren_tape_vjp(cfd_siren* h, const float* g_out, int64_t Ns, 
         size_t need = 0;
         cfd_siren_vjp_workspace_bytes(h, Ns, R, &need);
         CFD_REQUIRE(ws_bytes >= need, CFD_EARG, "workspace too small");
-        const int nh = h->cfg.num_hidden_layers, H = h->cfg.hidden_features, L = h->cfg.in_latent_features;
+        const size_t nf = (size_t)(h->cfg.num_hidden_layers + 1) * h->cfg.hidden_features;
         auto st = (hipStream_t)stream;
         cfd::SirenTapeArgs a{};
         tape_args(h, a, Ns, R, ws);
@@ -1581,23 +1608,8 @@ extern "C" int cfd_siren_tape_vjp(cfd_siren* h, const float* g_out, int64_t Ns, 
         a.ystride = y_stride;
         a.gout = g_out;
         launch_tape(h, a, true, st);
-        // g_z = (sum over sensors of delta) . V, as one fp32 MFMA GEMM
-        const int64_t nf = (int64_t)(nh + 1) * H;
-        if (L % 4 == 0 && nf % 16 == 0) {
-            float* D = (float*)ws + (size_t)R * nf + 2 * (size_t)R * Ns * nf;
-            hipLaunchKernelGGL(cfd::sensor_sum_kernel, dim3((unsigned)cfd::ceil_div(R * nf, 256)), dim3(256), 0, st,
-                               a.delta, D, (int)Ns, nf, (int64_t)R);
-            cfd::check_launch("sensor_sum_kernel");
-            cfd::launch_gemm_f32(false, D, (int)nf, h->V, L, nullptr, g_latents, L, R, L, (int)nf, st, D + R * nf);
-        } else {
-            const size_t lds = sizeof(float) * (size_t)(nh + 1) * H;
-            CFD_REQUIRE(lds <= 160 * 1024, CFD_EARG, "SIREN too deep for the latent-gradient reduction");
-            CFD_HIP(hipFuncSetAttribute((const void*)cfd::siren_latent_grad,
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL(cfd::siren_latent_grad, dim3(R), dim3(256), lds, st, a.delta, h->V, g_latents,
-                               (int)Ns, nh + 1, H, L);
-            cfd::check_launch("siren_latent_grad");
-        }
+        float* D = (float*)ws + (size_t)R * nf + 2 * (size_t)R * Ns * nf;
+        cfd::latent_grad_from_delta(h, a.delta, D, Ns, R, g_latents, st);
     });
 }
 

@@ -157,5 +157,8 @@ int gemm_splits(int K);
 void launch_gemm_f32(bool bt, const float* A, int lda, const float* B, int ldb, const float* bias, float* C, int ldc,
                      int M, int N, int K, hipStream_t st, float* part = nullptr);
 void film_vectors(const cfd_siren* h, const float* latents, int b, float* film, hipStream_t st);
+// g_z (R, L) from the tape deltas (R, Ns, nh+1, H); D: R (nh+1) H floats and the GEMM's split-K partials
+void latent_grad_from_delta(const cfd_siren* h, const float* delta, float* D, int64_t Ns, int R, float* g_latents,
+                            hipStream_t st);
 
 }  // namespace cfd

@@ -25,6 +25,16 @@ mask=mask)``, replaces the three SIREN / residual lines by one call,
 
     g_z, norm = cfd_siren_dense_grad(unnorm(x0), y, mask) (bounded workspace)
 
+SensorStencilOperator ('sensor_stencil': linear stencils on the value and the exact
+coordinate Jacobian at the sensors -- vorticity, divergence, wall shear) runs the
+Case4 sequence on the Jacobian tape, readings (T, Ns, M):
+
+    out, jac     = cfd_siren_jtape_forward(unnorm(x0))
+    g_out, g_jac = cfd_dps_residual_linear(y, out, jac, weights)
+    g_z          = cfd_siren_jtape_vjp(g_out, g_jac)
+
+A ``mask`` keyword with it raises NotImplementedError (a zero weight row does that).
+
 InpaintingOperator (A(x0) = mask * x0 on the latent image, measurements.py:40-56)
 needs no decoder: the three SIREN lines and cfd_dps_latent_grad become
 
@@ -67,7 +77,7 @@ from ..gaussian_diffusion import (KNOWN_COUNTER, LossType, ModelMeanType, ModelV
                                   broadcast_rows, check_model_range, fresh_seed, get_named_beta_schedule)
 from ..respace import SpacedDiffusion, space_timesteps
 from .condition_methods import Identity, PosteriorSampling
-from .measurements import Case4Operator, InpaintingOperator
+from .measurements import _STENCIL_MASK, Case4Operator, InpaintingOperator, SensorStencilOperator
 
 __SAMPLER__ = {}
 
@@ -247,6 +257,10 @@ class _GuidedSampler(SpacedDiffusion):
             if x.dim() != 4 or x.shape[1] != 1:
                 raise ValueError(f"latents must be (B, 1, T, L), got {tuple(x.shape)}")
             return _LatentMask(kw.get("mask"), measurement, x)
+        if isinstance(op, SensorStencilOperator):
+            if kw.get("mask") is not None:
+                raise NotImplementedError(_STENCIL_MASK)
+            return None
         return _mask_tables(kw.get("mask"), op, x.shape[0], x.shape[2], op.coords.shape[0], op.model.out_features,
                             x.device)
 
@@ -335,6 +349,11 @@ class _GuidedSampler(SpacedDiffusion):
             _lib.check(lib.cfd_dps_residual(_lib.ptr(y), 0 if y.numel() == per else per, _lib.ptr(A), _lib.ptr(gA),
                                             _lib.ptr(dist_out), per, B, st), "cfd_dps_residual")
             gz = op.vjp(gA)                                              # (B*T, L)
+        elif isinstance(op, SensorStencilOperator):
+            # value and derivative sensors: the Jacobian tape and its adjoint (K15)
+            out, jac = op.forward_tape(x0)                               # (B*T, Ns, c), (B*T, Ns, c, d)
+            _, g_out, g_jac, _ = op.residual(out, jac, y, B, dist_out)
+            gz = op.vjp(g_out, g_jac)                                    # (B*T, L)
         else:
             # a dense or masked measurement: norm and latent gradient in bounded memory
             gz, norms = op.dense_grad(x0, y, mask, self.dense_budget)

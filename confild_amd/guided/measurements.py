@@ -268,6 +268,128 @@ class Case4Operator(_SirenFieldOperator):
         return self.model.tape_vjp(g_out)
 
 
+@register_operator(name="sensor_stencil")
+class SensorStencilOperator(_SirenFieldOperator):
+    """Linear stencils on the decoded value and its exact coordinate Jacobian at Ns
+    sensors (no reference counterpart): M readings per sensor,
+
+        A[r, s, m] = sum_o wv[s, m, o] out[r, s, o] + sum_{o,k} wj[s, m, o, k] jac[r, s, o, k]
+
+    with ``value_weights`` (M, c) or per sensor (Ns, M, c) and ``jac_weights`` (M, c, d)
+    or (Ns, M, c, d); at least one of the two (confild_amd.guided.stencils builds
+    divergence, vorticity, directional-derivative and plain-value weights).  out and
+    jac are decode_jacobian's, in physical units.  The DPS sampler runs its adjoint
+    through the Jacobian tape (cfd_siren_jtape_forward / _vjp, cfd_dps_residual_linear).
+    A sensor or reading is switched off with a zero weight row; a ``mask`` keyword
+    is refused."""
+
+    _name = "SensorStencil"
+
+    def __init__(self, device, coords_path, batch_size, max_val_path, min_val_path, normalizer_params_path,
+                 ckpt_path, value_weights=None, jac_weights=None) -> None:
+        """Case4Operator's files (the SIREN's dimensions come from the checkpoint) and the
+        two weight arrays."""
+        self.device = device
+        self.coords = torch.tensor(np.load(coords_path), dtype=torch.float32, device=device)
+        params = torch.load(normalizer_params_path, weights_only=True, map_location="cpu")
+        x_uub, x_llb = params["x_normalizer_params"]
+        y_uub, _ = params["y_normalizer0u_params"]
+        _, y_llb = params["y_normalizer0l_params"]
+        sd = torch.load(ckpt_path, weights_only=True, map_location="cpu")["model_state_dict"]
+        cin_size, _, cout_size, _, _ = _siren_dims(sd)
+        self.x_normalizer = Normalizer_ts(method="-11", dim=0, params=(x_uub, x_llb))
+        self.y_normalizer = Normalizer_ts(method="-11", dim=0, params=(y_uub[:cout_size], y_llb[:cout_size]))
+        self._load_model(ckpt_path, cin_size, cout_size, device)
+        self.max_val = torch.from_numpy(np.load(max_val_path)).to(device)
+        self.min_val = torch.from_numpy(np.load(min_val_path)).to(device)
+        self.batch_size = batch_size
+        self._set_weights(value_weights, jac_weights)
+
+    @classmethod
+    def from_parts(cls, device, coords, x_normalizer, y_normalizer, model, max_val, min_val, batch_size=384,
+                   value_weights=None, jac_weights=None):
+        op = super().from_parts(device, coords, x_normalizer, y_normalizer, model, max_val, min_val, batch_size)
+        op._set_weights(value_weights, jac_weights)
+        return op
+
+    def _set_weights(self, value_weights, jac_weights):
+        if value_weights is None and jac_weights is None:
+            raise ValueError("SensorStencil needs value_weights, jac_weights or both")
+        Ns, c, d = self.coords.shape[0], self.model.out_features, self.model.in_coord_features
+        self.wv = self.wj = None
+        self.wv_per_sensor = self.wj_per_sensor = False
+        M = None
+        for name, w, tail in (("value_weights", value_weights, (c,)), ("jac_weights", jac_weights, (c, d))):
+            if w is None:
+                continue
+            w = torch.as_tensor(w, dtype=torch.float32)
+            shared, per = ("M",) + tail, (Ns, "M") + tail
+            if w.dim() == len(shared) and tuple(w.shape[1:]) == tail:
+                per_sensor, m = False, w.shape[0]
+            elif w.dim() == len(per) and w.shape[0] == Ns and tuple(w.shape[2:]) == tail:
+                per_sensor, m = True, w.shape[1]
+            else:
+                raise ValueError(f"{name} of shape {tuple(w.shape)} is neither {shared} nor {per}")
+            if m < 1 or (M is not None and m != M):
+                raise ValueError(f"{name} has {m} readings per sensor, expected {M if M is not None else 'at least 1'}")
+            M = m
+            w = w.to(self.coords.device).contiguous()
+            if name == "value_weights":
+                self.wv, self.wv_per_sensor = w, per_sensor
+            else:
+                self.wj, self.wj_per_sensor = w, per_sensor
+        self.readings = M
+
+    def residual(self, out, jac, y, B, norm_out=None, want_A=False):
+        """cfd_dps_residual_linear on (out (R, Ns, c), jac (R, Ns, c, d)): the B per-sample
+        norms ||y - A||, g_out and g_jac (None without the weight set), and A (R, Ns, M)
+        when asked for.  y: one sample's (T, Ns, M) readings or the batch's (R, Ns, M)."""
+        _require_gpu(out)
+        R, Ns, c = out.shape
+        d, M = self.model.in_coord_features, self.readings
+        if R % B:
+            raise ValueError(f"{R} rows do not split into {B} samples")
+        per = (R // B) * Ns * M
+        if y.numel() not in (per, per * B):
+            raise ValueError(f"measurement of {y.numel()} values matches neither one sample ({per}) "
+                             f"nor the batch ({per * B})")
+        y = y.to(device=out.device, dtype=torch.float32).contiguous()
+        g_out = torch.empty_like(out) if self.wv is not None else None
+        g_jac = torch.empty_like(jac) if self.wj is not None else None
+        norm = norm_out if norm_out is not None else torch.empty(B, dtype=torch.float32, device=out.device)
+        A = torch.empty((R, Ns, M), dtype=torch.float32, device=out.device) if want_A else None
+        _lib.check(_lib.lib().cfd_dps_residual_linear(
+            _lib.ptr(y), int(y.numel() == per * B and B > 1), _lib.ptr(out), _lib.ptr(jac), _lib.ptr(self.wv),
+            int(self.wv_per_sensor), _lib.ptr(self.wj), int(self.wj_per_sensor), _lib.ptr(g_out), _lib.ptr(g_jac),
+            _lib.ptr(norm), _lib.ptr(A), Ns, M, c, d, R // B, B, _lib.stream_of(out.device)),
+            "cfd_dps_residual_linear")
+        return norm, g_out, g_jac, A
+
+    def forward(self, data, **kwargs):
+        """(s, 1, t, l) latents in [-1, 1] -> (s*t, Ns, M) readings: decode_jacobian at the
+        sensors and the stencil contraction (cfd_dps_residual_linear's A)."""
+        if kwargs.get("mask") is not None:
+            raise NotImplementedError(_STENCIL_MASK)
+        with torch.no_grad():
+            out, jac = self.model.decode_jacobian(self.coords, self._rows(data)[:, None], self.x_normalizer,
+                                                  self.y_normalizer)
+        R = out.shape[0]
+        zero = torch.zeros((R, self.coords.shape[0], self.readings), dtype=torch.float32, device=out.device)
+        return self.residual(out.contiguous(), jac.contiguous(), zero, 1, want_A=True)[3]
+
+    # the adjoint: the whole Jacobian tape in memory (cfd_siren_jtape_forward / _vjp)
+    def forward_tape(self, data):
+        return self.model.jac_tape_forward(self.coords, self._rows(data), self.x_normalizer, self.y_normalizer)
+
+    def vjp(self, g_out=None, g_jac=None):
+        """gradient w.r.t. the un-normalised latent rows of the last forward_tape."""
+        return self.model.jac_tape_vjp(g_out, g_jac)
+
+
+_STENCIL_MASK = ("the 'sensor_stencil' operator takes no mask keyword: switch a sensor or a reading off with a "
+                 "zero weight row")
+
+
 # =============
 # Noise classes
 # =============

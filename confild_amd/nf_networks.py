@@ -386,6 +386,58 @@ class SIRENAutodecoder_film(nn.Module):
                    "cfd_siren_tape_vjp")
         return gz
 
+    # -- latent gradient of value and Jacobian functionals (K15: cfd_siren_jtape_*) ----
+    def jac_tape_forward(self, coords, latents, x_normalizer=None, y_normalizer=None):
+        """decode_jacobian() of R latent rows (R, L) at Ns points (Ns, d) -> (out (R, Ns, c),
+        jac (R, Ns, c, d)), keeping every layer's value and tangent accumulators for
+        jac_tape_vjp.  Always the exact fp32 chain; only '-11' normalisers (fused)."""
+        d, L, c = self.in_coord_features, self.in_latent_features, self.out_features
+        dev = latents.device
+        if dev.type != "cuda":
+            raise _lib.CfdError("SIREN jac_tape_forward needs GPU tensors (the HIP path has no CPU fallback)")
+        cf = coords.reshape(-1, d).to(device=dev, dtype=torch.float32).contiguous()
+        lat = latents.detach().reshape(-1, L).to(torch.float32).contiguous()
+        Ns, R = cf.shape[0], lat.shape[0]
+        cf, xmax, xmin, ymax, ymin, ystride, post = self._norm_args(cf, Ns, dev, x_normalizer, y_normalizer)
+        if post is not None or (x_normalizer is not None and xmax is None):
+            raise NotImplementedError("the SIREN Jacobian adjoint fuses '-11' normalisers only")
+        h = self._handle(dev)
+        lib = _lib.load()
+        n = C.c_size_t()
+        _lib.check(lib.cfd_siren_jtape_workspace_bytes(h, Ns, R, C.byref(n)), "siren jtape workspace")
+        ws = torch.empty(max(n.value, 16), dtype=torch.uint8, device=dev)
+        out = torch.empty((R, Ns, c), dtype=torch.float32, device=dev)
+        jac = torch.empty((R, Ns, c, d), dtype=torch.float32, device=dev)
+        _lib.check(lib.cfd_siren_jtape_forward(h, _lib.ptr(cf), Ns, _lib.ptr(lat), R, _lib.ptr(xmax), _lib.ptr(xmin),
+                                               _lib.ptr(ymax), _lib.ptr(ymin), ystride, _lib.ptr(out), _lib.ptr(jac),
+                                               _lib.ptr(ws), ws.numel(), _lib.stream_of(dev)),
+                   "cfd_siren_jtape_forward")
+        # keep every buffer the kernels read until jac_tape_vjp
+        self._jvjp_tape = (ws, Ns, R, ymax, ymin, ystride, cf, lat, xmax, xmin, self._signature())
+        return out, jac
+
+    def jac_tape_vjp(self, g_out=None, g_jac=None):
+        """d(<g_out, out> + <g_jac, jac>)/d latents -> (R, L), for the last
+        jac_tape_forward; a gradient left None is zero."""
+        tape = getattr(self, "_jvjp_tape", None)
+        if tape is None:
+            raise RuntimeError("jac_tape_vjp needs a preceding jac_tape_forward")
+        ws, Ns, R, ymax, ymin, ystride, _, _, _, _, sig = tape
+        if sig != self._signature():
+            raise RuntimeError("parameters changed since jac_tape_forward")
+        c, d = self.out_features, self.in_coord_features
+        for name, g, shape in (("g_out", g_out, (R, Ns, c)), ("g_jac", g_jac, (R, Ns, c, d))):
+            if g is not None and (tuple(g.shape) != shape or g.device != ws.device):
+                raise ValueError(f"{name} must match the output of the last jac_tape_forward")
+        g0 = None if g_out is None else g_out.detach().to(torch.float32).contiguous()
+        g1 = None if g_jac is None else g_jac.detach().to(torch.float32).contiguous()
+        gz = torch.empty((R, self.in_latent_features), dtype=torch.float32, device=ws.device)
+        h = self._handle(ws.device)
+        _lib.check(_lib.load().cfd_siren_jtape_vjp(h, _lib.ptr(g0), _lib.ptr(g1), Ns, R, _lib.ptr(ymax),
+                                                   _lib.ptr(ymin), ystride, _lib.ptr(gz), _lib.ptr(ws), ws.numel(),
+                                                   _lib.stream_of(ws.device)), "cfd_siren_jtape_vjp")
+        return gz
+
     # -- dense masked DPS adjoint (K12: cfd_siren_dense_grad) ------------------------
     DENSE_BACKWARD = {"sum": 0, "delta": 1}
     DENSE_COMPUTE = {"auto": 0, "f32": 1}

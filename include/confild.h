@@ -437,6 +437,46 @@ int  cfd_siren_tape_vjp(cfd_siren* h, const float* g_out, int64_t Ns, int R,
                         const float* ymax, const float* ymin, int64_t y_stride,
                         float* g_latents, void* workspace, size_t ws_bytes, void* stream);
 
+/* Latent gradient of a linear functional of the value and the coordinate Jacobian
+ * at sensor points (K15: derivative sensors in the DPS sampler; no reference
+ * counterpart).  cfd_siren_jtape_forward = cfd_siren_forward_jacobian over Ns sensor
+ * coordinates for R latent rows (out (R, Ns, c), jac (R, Ns, c, d), physical units,
+ * both required), keeping every layer's value and tangent accumulators in the
+ * workspace; cfd_siren_jtape_vjp:
+ *   g_latents (R, L) = d( <g_out, out> + <g_jac, jac> ) / d latents
+ * for that forward (same h, Ns, R, workspace and y normaliser).  g_out (R, Ns, c) and
+ * g_jac (R, Ns, c, d) may each be NULL, which means zero.  Always the exact fp32 MFMA
+ * chain, whatever cfd_siren_set_compute chose; deterministic, and a row's result does
+ * not depend on R or on the other rows.
+ * Workspace (16-byte aligned), with nl = num_hidden_layers + 1, H = hidden_features,
+ * P = R Ns, nf = nl H: (2 + d) P nf floats of tape and deltas + 2 R nf (FiLM vectors,
+ * sensor sums) + the latent GEMM's split-K partials; ask cfd_siren_jtape_workspace_bytes.
+ * CFD_EARG before any launch: a NULL required pointer, Ns < 1 or > 2^20, R < 1,
+ * normaliser bounds not in pairs, a workspace even one byte short and
+ * in_coord_features = 4.  Widths: hidden_features = 16*{1,2,3,4,6,8,12,16,24,32}
+ * (512 runs 4 waves per workgroup, none uses scratch). */
+int  cfd_siren_jtape_workspace_bytes(const cfd_siren* h, int64_t Ns, int R, size_t* bytes);
+int  cfd_siren_jtape_forward(cfd_siren* h, const float* coords, int64_t Ns, const float* latents, int R,
+                             const float* xmax, const float* xmin,
+                             const float* ymax, const float* ymin, int64_t y_stride,
+                             float* out, float* jac, void* workspace, size_t ws_bytes, void* stream);
+int  cfd_siren_jtape_vjp(cfd_siren* h, const float* g_out, const float* g_jac, int64_t Ns, int R,
+                         const float* ymax, const float* ymin, int64_t y_stride,
+                         float* g_latents, void* workspace, size_t ws_bytes, void* stream);
+/* The residual of linear sensor stencils on (out, jac) of cfd_siren_jtape_forward:
+ *   A[r, s, m] = sum_o wv[s, m, o] out[r, s, o] + sum_{o,k} wj[s, m, o, k] jac[r, s, o, k]
+ * wv (M, c) or, with wv_per_sensor, (Ns, M, c); wj (M, c, d) or (Ns, M, c, d); either
+ * may be NULL (with its gradient output), not both.  y: rows_per_sample tables of
+ * (Ns, M) shared by the B samples, or with y_per_sample B rows_per_sample of them.
+ * Per sample b (rows [b T, (b+1) T), T = rows_per_sample): norm[b] = ||y - A||_2
+ * (float64 sum in a fixed order), g_out = wv^T g and g_jac = wj^T g with
+ * g = -(y - A) / norm[b] (zero where the norm is zero, as cfd_dps_residual).
+ * A (R, Ns, M) is written when not NULL.  c <= 4, d <= 3. */
+int  cfd_dps_residual_linear(const float* y, int y_per_sample, const float* out, const float* jac,
+                             const float* wv, int wv_per_sensor, const float* wj, int wj_per_sensor,
+                             float* g_out, float* g_jac, float* norm, float* A, int64_t Ns, int M, int c,
+                             int d, int rows_per_sample, int B, void* stream);
+
 /* Dense masked DPS adjoint (Case2 / Case3 operators: a whole field of N points,
  * measurements.py:58-181): the masked residual norm and its latent gradient in
  * one call whose workspace is bounded by `budget` and does not grow with N.

@@ -27,70 +27,9 @@
 // the second-order update is one fixed fmaf sequence, the same in every instantiation.
 #include <algorithm>
 
-#include "siren.hpp"
+#include "siren_hess.hpp"
 
 namespace cfd {
-
-struct SirenHessArgs {
-    const float* w0;      // (H, d)
-    const float* wimg;    // hidden weight image (as SirenArgs)
-    const float* wout;    // (c, H)
-    const float* bout;    // (c)
-    const float* film;    // (b, nh+1, H)
-    const float* coords;  // (N, d)
-    const float* xmax;
-    const float* xmin;
-    const float* ymax;
-    const float* ymin;
-    float* out;           // (b, N, c) or null
-    float* jac;           // (b, N, c, d) or null
-    float* hess;          // (b, N, c, d, d), or (b, N, c, d) with diag
-    int64_t N;
-    int64_t ystride;
-    int64_t b0;
-    int b;                // latent rows of the call (index assertions)
-    int d, c, nh;
-    int nsec;             // second-order roles: d (diagonal only) or d (d + 1) / 2
-    int diag;             // hess holds the diagonal only
-    float w0f;
-};
-
-// sin(x) where value is set, cos(x) elsewhere, from one reduction (K13's sincos_role,
-// bit for bit sin_cw / cos_cw of common.hpp): "x - qq * (pi/2 split)" with qq = 2q
-// (sine) or the odd q' (cosine), one shared polynomial; sin: negate for odd q
-// (qq & 2), cos: negate unless qq & 2.
-__device__ __forceinline__ float hess_sincos_role(float x, bool value) {
-    const float t = fmaf(x, 0.318309886183790671538f, value ? 0.0f : -0.5f);
-    const float qq = fmaf(2.0f, rintf(t), value ? 0.0f : 1.0f);
-    float r = fmaf(qq, -1.5703125f, x);
-    r = fmaf(qq, -0.00048351287841796875f, r);
-    r = fmaf(qq, -3.13855707645416259765625e-07f, r);
-    r = fmaf(qq, -6.077100628276710381e-11f, r);
-    const float s = r * r;
-    float u = 2.6083159809786593541503e-06f;
-    u = fmaf(u, s, -0.0001981069071916863322258f);
-    u = fmaf(u, s, 0.00833307858556509017944336f);
-    u = fmaf(u, s, -0.166666597127914428710938f);
-    const float y = fmaf(s, u * r, r);
-    const bool neg = (((unsigned)(int)qq & 2u) != 0u) == value;
-    const float v = __uint_as_float(__float_as_uint(y) ^ (neg ? (1u << 31) : 0u));
-    const float xr = x * 0.159154943091895335768f;
-    const float hw = value ? __builtin_amdgcn_sinf(xr) : __builtin_amdgcn_cosf(xr);
-    return fabsf(x) < 39000.0f ? v : hw;
-}
-
-// v of the lane whose byte address (4 * lane) is addr: ds_bpermute_b32, no LDS memory
-__device__ __forceinline__ float lane_value(int addr, float v) {
-    return __int_as_float(__builtin_amdgcn_ds_bpermute(addr, __float_as_int(v)));
-}
-
-// the second-order update of one element, one fixed order for every form:
-// w0 cos u * h - ((w0^2 sin u) * ak) * al
-__device__ __forceinline__ float second_order(float w0f, float w0sq, float su, float cu, float h, float ak,
-                                              float al) {
-    const float t = ((w0sq * su) * ak) * al;
-    return fmaf(w0f * cu, h, -t);
-}
 
 template <int NB, int RS, int WAVES>
 __global__ __launch_bounds__(64 * WAVES, NB <= 24 ? 2 : 1) void siren_hess_fused(SirenHessArgs p) {
@@ -108,26 +47,10 @@ __global__ __launch_bounds__(64 * WAVES, NB <= 24 ? 2 : 1) void siren_hess_fused
     const int j16 = lane & 15;
     const int role = j16 & (RS - 1);
     const int d = p.d;
-    const int sidx = role - 1 - d;     // index among the second-order roles
-    const bool value = role == 0;
-    const bool tangent = role >= 1 && role <= d;
-    const bool second = sidx >= 0 && sidx < p.nsec;
-    // the coordinates (k, l), k <= l, of this column: tangent k = l = role - 1; second
-    // order xx, yy, zz, then xy, xz, yz
-    int ck = 0, cl = 0;
-    if (tangent) ck = cl = role - 1;
-    if (second) {
-        const int pr = sidx - d;
-        ck = pr < 0 ? sidx : pr == 2 ? 1 : 0;
-        cl = pr < 0 ? sidx : pr == 0 ? 1 : 2;
-    }
-    // byte addresses (ds_bpermute) of the group's value column, of tangents k and l and
-    // of the column whose cosine this one reads
-    const int base = lane - role;
-    const int src_v = 4 * base;
-    const int src_k = second ? 4 * (base + 1 + ck) : 4 * lane;
-    const int src_l = second ? 4 * (base + 1 + cl) : 4 * lane;
-    const int src_c = 4 * (base + 1);  // the first tangent column: cos u
+    const HessRole R = hess_role(lane, role, d, p.nsec);
+    const bool value = R.value, tangent = R.tangent, second = R.second;
+    const int ck = R.ck, cl = R.cl;
+    const int src_v = R.src_v, src_k = R.src_k, src_l = R.src_l, src_c = R.src_c;
     const int64_t b = p.b0 + blockIdx.y;
     const int64_t n = (int64_t)blockIdx.x * TILE + wave * PPW + j16 / RS;
     const int64_t nc = n < p.N ? n : p.N - 1;
@@ -237,58 +160,9 @@ __global__ __launch_bounds__(64 * WAVES, NB <= 24 ? 2 : 1) void siren_hess_fused
     }
 
     // ---- last layer (H -> c) per column; value: bias + de-normalisation, others: their slope ----
-    float o[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int oc = 0; oc < 4; ++oc) {
-        if (oc < p.c) {
-            const float* wr = p.wout + oc * H + 4 * g;
-            float s = 0.f;
-            static_for<NB>([&](auto qc) {
-                constexpr int q = decltype(qc)::value;
-                const f4 w = *(const f4*)(wr + 16 * q);
-                s = fmaf(w.x, X[q][0], s);
-                s = fmaf(w.y, X[q][1], s);
-                s = fmaf(w.z, X[q][2], s);
-                s = fmaf(w.w, X[q][3], s);
-            });
-            s += __shfl_xor(s, 16);
-            s += __shfl_xor(s, 32);
-            o[oc] = value ? s + p.bout[oc] : s;
-        }
-    }
-    if (n < p.N && g < p.c && (value || tangent || second)) {
-        float v = g == 0 ? o[0] : g == 1 ? o[1] : g == 2 ? o[2] : o[3];
-        float hi = 1.0f, lo = -1.0f;
-        if (p.ymax) {
-            const int64_t yi = n * p.ystride + g;
-            hi = p.ymax[yi];
-            lo = p.ymin[yi];
-        }
-        const int64_t oi = (b * p.N + n) * p.c + g;
-        [[maybe_unused]] const int64_t no = (int64_t)p.b * p.N * p.c;
-        CFD_DASSERT(oi >= 0 && oi < no);
-        if (value) {
-            if (p.ymax) v = (v + 1.0f) / 2.0f * (hi - lo) + lo;
-            if (p.out) p.out[oi] = v;
-        } else {
-            if (p.ymax) v = v * ((hi - lo) / 2.0f);
-            if (tangent) {
-                const int64_t ji = oi * d + ck;
-                CFD_DASSERT(ji >= 0 && ji < no * d);
-                if (p.jac) p.jac[ji] = v;
-            } else if (p.diag) {
-                const int64_t di = oi * d + ck;
-                CFD_DASSERT(di >= 0 && di < no * d);
-                if (ck == cl) p.hess[di] = v;
-            } else {
-                // both halves from the same lane: symmetric to the bit
-                const int64_t h0 = (oi * d + ck) * d + cl, h1 = (oi * d + cl) * d + ck;
-                CFD_DASSERT(h0 >= 0 && h0 < no * d * d && h1 >= 0 && h1 < no * d * d);
-                p.hess[h0] = v;
-                if (ck != cl) p.hess[h1] = v;
-            }
-        }
-    }
+    float o[4];
+    hess_head<NB>(p, X, g, value, o);
+    hess_store(p, R, o, n, b, g);
 }
 
 }  // namespace cfd

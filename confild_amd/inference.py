@@ -47,6 +47,14 @@ reference-preserving defaults:
                                launch per chunk, which leaves the files above as they are: hessian
                                (..., c, d, d), laplacian (..., c), grad_divergence (..., d).  laplacian
                                alone runs the diagonal form)
+                               Also the PDE residuals of confild_amd.derived, from the launches above and
+                               the chunk's saved fields: convective_acceleration (..., d), (u . grad) u
+                               from the Jacobian launch; momentum_residual (..., d), the steady form
+                               u . grad u + grad p / rho - nu lap u from the Hessian launch's Jacobian and
+                               Hessian (no time derivative: dudt is not a driver feature);
+                               pressure_poisson_residual (...), lap p + rho d_i u_k d_k u_i from the
+                               Hessian launch.  The two residuals need the Laplacian only: with no hessian
+                               or grad_divergence beside them the diagonal form runs)
   derived_compute: f32        (f32 | split_f16: the arithmetic of the Jacobian launch behind jacobian |
                                vorticity | divergence | q_criterion.  f32: the exact fp32 MFMA chain;
                                split_f16: the same chain on the f16 matrix pipes with fp32-level
@@ -54,7 +62,17 @@ reference-preserving defaults:
                                hidden_features 32*{1,2,3,4,6,8,12}, num_hidden_layers >= 1, dims <= 3 --
                                any other value or width is a ValueError before sampling starts.  The
                                fields and the Hessian names do not depend on it)
+  derived_hessian_compute: f32 (f32 | split_f16: the arithmetic of the Hessian launch behind hessian |
+                               laplacian | grad_divergence | momentum_residual | pressure_poisson_residual.
+                               split_f16 is decode_hessian(compute="split_f16"), with derived_compute's
+                               widths and the same ValueError before sampling starts.  derived_compute
+                               stays the Jacobian launch's alone)
   derived_velocity_channels:  (which d output channels are the velocity, default the first d)
+  derived_nu:                 (float, the kinematic viscosity: required with momentum_residual)
+  derived_rho: 1.0            (float, the density of the two residuals)
+  derived_pressure_channel: null   (int, the output channel that is the pressure: required with
+                               pressure_poisson_residual; null drops the pressure term of momentum_residual.
+                               It must not be one of the velocity channels)
 Known deviation (fixed on purpose): ``channel_mult`` from the YAML IS passed to
 create_model (the reference reads but drops it, inference.py:38-44, so its own
 case4.yml raises ValueError).
@@ -123,8 +141,10 @@ def rollout_sampler(inp, diff, sampler):
                           timestep_respacing=getattr(inp, "timestep_respacing", "")), method
 
 
-HESSIAN_DERIVED = ("hessian", "laplacian", "grad_divergence")      # from infer_hessian, the rest from infer_jacobian
-DERIVED = ("jacobian", "vorticity", "divergence", "q_criterion") + HESSIAN_DERIVED
+RESIDUAL_DERIVED = ("momentum_residual", "pressure_poisson_residual")   # the Laplacian is all they need
+# from infer_hessian, the rest from infer_jacobian
+HESSIAN_DERIVED = ("hessian", "laplacian", "grad_divergence") + RESIDUAL_DERIVED
+DERIVED = ("jacobian", "vorticity", "divergence", "q_criterion", "convective_acceleration") + HESSIAN_DERIVED
 
 
 def derived_names(inp):
@@ -155,10 +175,69 @@ def derived_compute(inp):
     return mode
 
 
-def derived_quantity(name, jac, velocity_channels=None, hess=None, diag=False):
+def derived_hessian_compute(inp):
+    """The ``derived_hessian_compute`` YAML key: "f32" (default) or "split_f16", the
+    arithmetic of the Hessian launch, checked against the CNF case file as
+    derived_compute() checks the Jacobian launch's."""
+    from .nf_networks import HESSIAN_COMPUTE, hessian_split_refusal
+    mode = str(getattr(inp, "derived_hessian_compute", None) or "f32")
+    if mode not in HESSIAN_COMPUTE:
+        raise ValueError(f"derived_hessian_compute must be one of {list(HESSIAN_COMPUTE)}, got {mode!r}")
+    if mode == "split_f16":
+        cnf = basic_input(inp.cnf_case_file_path)
+        why = hessian_split_refusal(int(cnf.dims), int(cnf.NF["num_hidden_layers"]), int(cnf.NF["hidden_features"]))
+        if why:
+            raise ValueError(f"derived_hessian_compute: split_f16 does not take this CNF: {why}")
+    return mode
+
+
+def derived_physics(inp, names=None):
+    """{nu, rho, pressure_channel} of the residual names, from ``derived_nu``,
+    ``derived_rho`` and ``derived_pressure_channel``, checked against ``names`` (default:
+    the ``derived`` key) and the CNF case file's out_features (no model is loaded)."""
+    names = derived_names(inp) if names is None else names
+    nu, rho, pch = (getattr(inp, k, None) for k in ("derived_nu", "derived_rho", "derived_pressure_channel"))
+
+    def number(key, v):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not np.isfinite(v):
+            raise ValueError(f"{key} must be a finite number, got {v!r}")
+        return float(v)
+    nu = None if nu is None else number("derived_nu", nu)
+    rho = 1.0 if rho is None else number("derived_rho", rho)
+    if rho == 0.0:
+        raise ValueError("derived_rho must not be 0")
+    if "momentum_residual" in names and nu is None:
+        raise ValueError("derived: momentum_residual needs derived_nu")
+    if "pressure_poisson_residual" in names and pch is None:
+        raise ValueError("derived: pressure_poisson_residual needs derived_pressure_channel")
+    if pch is not None:
+        if isinstance(pch, bool) or not isinstance(pch, int):
+            raise ValueError(f"derived_pressure_channel must be an integer or null, got {pch!r}")
+        c = int(basic_input(inp.cnf_case_file_path).NF["out_features"])
+        if pch < 0 or pch >= c:
+            raise ValueError(f"derived_pressure_channel {pch} out of range for {c} components")
+        # the pressure is not a velocity component: derived_velocity_channels, or the first d
+        vch = getattr(inp, "derived_velocity_channels", None)
+        vch = list(range(int(basic_input(inp.cnf_case_file_path).dims))) if vch is None else [int(v) for v in vch]
+        if pch in vch:
+            raise ValueError(f"derived_pressure_channel {pch} is one of the velocity channels {vch}")
+    return {"nu": nu, "rho": rho, "pressure_channel": pch}
+
+
+def derived_quantity(name, jac, velocity_channels=None, hess=None, diag=False, fields=None, physics=None):
     """One ``derived`` quantity of a Jacobian (..., c, d) or, for HESSIAN_DERIVED, of a
-    Hessian (..., c, d, d) (``diag``: its diagonal form (..., c, d), enough for laplacian)."""
+    Hessian (..., c, d, d) (``diag``: its diagonal form (..., c, d), enough for laplacian
+    and the residuals).  convective_acceleration and momentum_residual also read the
+    ``fields`` (..., c); the residuals take ``physics`` (derived_physics())."""
     from . import derived
+    if name == "convective_acceleration":
+        return derived.convective_acceleration(fields, jac, velocity_channels)
+    if name == "momentum_residual":
+        return derived.momentum_residual(fields, jac, hess, physics["nu"], physics["pressure_channel"],
+                                         physics["rho"], velocity_channels=velocity_channels)
+    if name == "pressure_poisson_residual":
+        return derived.pressure_poisson_residual(jac, hess, physics["pressure_channel"], physics["rho"],
+                                                 velocity_channels)
     if name == "jacobian":
         return jac
     if name == "hessian":
@@ -218,6 +297,8 @@ def run(yaml_path: str):
         raise _lib.CfdError("confild_amd.inference needs a GPU")
     inp = basic_input(yaml_path)
     jcompute = derived_compute(inp)                          # raises before any model is built
+    hcompute = derived_hessian_compute(inp)                  # the same for the Hessian launch
+    physics = derived_physics(inp)                           # and the residuals' keys
     seed = int(getattr(inp, "seed", 42))
     torch.manual_seed(seed)
     np.random.seed(seed)
@@ -291,11 +372,15 @@ def run(yaml_path: str):
     c, d = cnf.nf.out_features, cnf.nf.in_coord_features
     jnames = [n for n in names if n not in HESSIAN_DERIVED]
     hnames = [n for n in names if n in HESSIAN_DERIVED]
-    diag = hnames == ["laplacian"]                           # the unmixed derivatives are all it needs
+    # the unmixed derivatives are all a Laplacian needs, and the residuals need the Laplacian only
+    diag = bool(hnames) and all(n == "laplacian" or n in RESIDUAL_DERIVED for n in hnames)
     hd = d if diag else d * d
     # rows per launch bounded by ~2 GiB of output (with `derived`: the fields and their (c, d) Jacobian;
-    # with a Hessian name also that launch's fields, Jacobian and (c, d, d) or (c, d) Hessian)
-    rows = max(1, (2 << 30) // (npts * c * 4 * ((1 + d if jnames else 1) + (1 + d + hd if hnames else 0))))
+    # with a Hessian name also that launch's fields, Jacobian and (c, d, d) or (c, d) Hessian; the
+    # PDE-residual names keep up to (c, d) floats of intermediates of their own per point and name)
+    nres = sum(n in RESIDUAL_DERIVED or n == "convective_acceleration" for n in names)
+    rows = max(1, (2 << 30) // (npts * c * 4 * ((1 + d if jnames else 1) + (1 + d + hd if hnames else 0) +
+                                                nres * d)))
     fields, extra = [], {n: [] for n in names}
     s, e = dist.shard_range(B * T, rank, world)
     for a in range(s, e, rows):
@@ -306,17 +391,18 @@ def run(yaml_path: str):
         if jnames:
             jac = cnf.infer_jacobian(coord, chunk, compute=jcompute)[1]
             for n in jnames:
-                extra[n].append(derived_quantity(n, jac, vch))
+                extra[n].append(derived_quantity(n, jac, vch, fields=fields[-1]))
         if hnames:
-            hess = cnf.infer_hessian(coord, chunk, diag=diag)[2]
+            _, hjac, hess = cnf.infer_hessian(coord, chunk, diag=diag, compute=hcompute)
             for n in hnames:
-                extra[n].append(derived_quantity(n, None, vch, hess, diag))
+                extra[n].append(derived_quantity(n, hjac, vch, hess, diag, fields[-1], physics))
     local = {"": torch.cat(fields) if fields else torch.empty((0,) + spatial + (c,), device=device)}
     for n in names:
         local[n] = (torch.cat(extra[n]) if extra[n] else
                     derived_quantity(n, torch.empty((0,) + spatial + (c, d), device=device), vch,
                                      torch.empty((0,) + spatial + (c,) + (d,) * (1 if diag else 2), device=device),
-                                     diag)).contiguous()
+                                     diag, torch.empty((0,) + spatial + (c,), device=device),
+                                     physics)).contiguous()
     if world > 1:   # gather the decoded fields to rank 0 over RCCL
         sizes = [dist.shard_range(B * T, r, world)[1] - dist.shard_range(B * T, r, world)[0] for r in range(world)]
         local = {n: dist.gather_cat(v, 0, sizes, dst=0) for n, v in local.items()}

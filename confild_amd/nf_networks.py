@@ -81,6 +81,26 @@ def jacobian_split_supported(d, nh, H):
     return jacobian_split_refusal(d, nh, H) is None
 
 
+HESSIAN_COMPUTE = JACOBIAN_COMPUTE                      # decode_hessian(compute=...)
+
+
+def hessian_split_refusal(d, nh, H):
+    """Why decode_hessian(compute="split_f16") refuses a network of ``d`` coordinate
+    features, ``nh`` hidden layers of width ``H`` (the rule of
+    cfd_siren_forward_hessian_split, no library call), or None when it runs.  K14s
+    takes K13s's widths with K13s's LDS staging, so this is jacobian_split_refusal's
+    rule (the value, tangent and second-order chains of a point share 16 MFMA columns)."""
+    if not 1 <= d <= 3:
+        return (f"in_coord_features must be 1..3, got {d} (the value, tangent and second-order chains of a point "
+                "share 16 MFMA columns)")
+    return jacobian_split_refusal(d, nh, H)
+
+
+def hessian_split_supported(d, nh, H):
+    """True when decode_hessian(compute="split_f16") takes these widths."""
+    return hessian_split_refusal(d, nh, H) is None
+
+
 class SIRENAutodecoder_film(nn.Module):
     """Constructor as nf_networks.py:447-478 (sine nonlinearity, no premap)."""
 
@@ -307,13 +327,20 @@ class SIRENAutodecoder_film(nn.Module):
         return out.reshape((b,) + spatial + (c,)), jac.reshape((b,) + spatial + (c, d))
 
     # -- value, Jacobian and coordinate Hessian (K14: cfd_siren_forward_hessian) ------
-    def decode_hessian(self, coords, latents, x_normalizer=None, y_normalizer=None, diag=False):
+    def decode_hessian(self, coords, latents, x_normalizer=None, y_normalizer=None, diag=False, compute=None):
         """decode_jacobian() together with the exact second spatial derivatives, one
         fused launch: returns (out, jac, hess) with hess (b, *spatial, c, d, d),
         hess[..., o, k, l] = d2 out[..., o] / d coords[..., k] d coords[..., l] in
         physical units, symmetric to the bit; ``diag=True`` returns (b, *spatial, c, d),
         the unmixed derivatives alone (all a Laplacian needs: half the columns at d = 3).
-        Broadcasting, normalisers and compute mode as decode_jacobian()."""
+        Broadcasting and normalisers as decode_jacobian().  ``compute``: None or "f32",
+        the exact fp32 chain (K14), whatever set_compute chose; "split_f16", the same
+        chain on the f16 matrix pipes with fp32-level accuracy (K14s,
+        cfd_siren_forward_hessian_split; the handle's compute mode is left alone), for
+        the widths hessian_split_supported() names -- any other width is a CfdError,
+        never a fall-back."""
+        if compute not in (None,) + HESSIAN_COMPUTE:
+            raise ValueError(f"compute must be None or one of {list(HESSIAN_COMPUTE)}, got {compute!r}")
         d, L, c = self.in_coord_features, self.in_latent_features, self.out_features
         dev = latents.device
         if dev.type != "cuda":
@@ -333,11 +360,11 @@ class SIRENAutodecoder_film(nn.Module):
         out = torch.empty((b, N, c), dtype=torch.float32, device=dev)
         jac = torch.empty((b, N, c, d), dtype=torch.float32, device=dev)
         hess = torch.empty((b, N) + hshape, dtype=torch.float32, device=dev)
-        _lib.check(lib.cfd_siren_forward_hessian(h, _lib.ptr(cf), N, _lib.ptr(lat), b, _lib.ptr(xmax),
-                                                 _lib.ptr(xmin), _lib.ptr(ymax), _lib.ptr(ymin), ystride,
-                                                 _lib.ptr(out), _lib.ptr(jac), _lib.ptr(hess), int(bool(diag)),
-                                                 _lib.ptr(ws), ws.numel(), _lib.stream_of(dev)),
-                   "cfd_siren_forward_hessian")
+        name = "cfd_siren_forward_hessian_split" if compute == "split_f16" else "cfd_siren_forward_hessian"
+        _lib.check(getattr(lib, name)(h, _lib.ptr(cf), N, _lib.ptr(lat), b, _lib.ptr(xmax), _lib.ptr(xmin),
+                                      _lib.ptr(ymax), _lib.ptr(ymin), ystride, _lib.ptr(out), _lib.ptr(jac),
+                                      _lib.ptr(hess), int(bool(diag)), _lib.ptr(ws), ws.numel(),
+                                      _lib.stream_of(dev)), name)
         return (out.reshape((b,) + spatial + (c,)), jac.reshape((b,) + spatial + (c, d)),
                 hess.reshape((b,) + spatial + hshape))
 

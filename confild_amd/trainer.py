@@ -93,17 +93,18 @@ class trainer:
             return self.nf.decode_jacobian(coord, latents.reshape(latents.shape[0], -1)[:, None],
                                            self.in_normalizer, self.out_normalizer, compute=compute)
 
-    def infer_hessian(self, coord, latents, diag=False):
+    def infer_hessian(self, coord, latents, diag=False, compute=None):
         """infer_jacobian() with the exact second derivatives: (fields, jac, hess), hess
         (b, N, c, d, d), or (b, N, c, d) with ``diag`` (the unmixed derivatives alone), in
-        physical units (SIRENAutodecoder_film.decode_hessian); grid coordinates keep
-        their shape as in infer()."""
+        physical units (SIRENAutodecoder_film.decode_hessian, which ``compute`` -- None,
+        "f32" or "split_f16" -- is passed to); grid coordinates keep their shape as in
+        infer()."""
         coord = coord if coord is not None else self.train_coord
         if coord is None:
             raise ValueError("no query coordinates: pass coord (infer_mode=True has no training points)")
         with torch.no_grad():
             return self.nf.decode_hessian(coord, latents.reshape(latents.shape[0], -1)[:, None],
-                                          self.in_normalizer, self.out_normalizer, diag=diag)
+                                          self.in_normalizer, self.out_normalizer, diag=diag, compute=compute)
 
     def load(self, checkpoint_id: int, siren_only=False):
         """train.py:481-528: newest checkpoint_*.pt when checkpoint_id == -1."""

@@ -420,6 +420,26 @@ int  cfd_siren_forward_hessian(cfd_siren* h, const float* coords, int64_t N, con
                                const float* ymax, const float* ymin, int64_t y_stride,
                                float* out, float* jac, float* hess, int diag_only,
                                void* workspace, size_t ws_bytes, void* stream);
+/* cfd_siren_forward_hessian on the f16 matrix pipes with fp32-level accuracy
+ * (csrc/siren_hess_split.hip, K14s): cfd_siren_forward_jacobian_split's arithmetic
+ * (three v_mfma_f32_16x16x32_f16 on hi/lo f16 halves per 32 features) with the
+ * second-order columns.  Every tangent and second-order column is split at a
+ * power-of-two scale of its own, taken per layer from the column's largest magnitude;
+ * the second-order update, a product of two tangent columns, is formed in the larger
+ * of the two frames it meets, and every scale is undone exactly at the head: no
+ * finite column overflows an f16 half, and scaling coordinate k by a power of two
+ * scales jac[.., k] and hess[.., k, l] by exactly its inverse (twice for k = l).
+ * Same parameters, NULL out / jac, diag_only, normaliser forms, workspace
+ * (cfd_siren_hessian_workspace_bytes), symmetry and invariances as
+ * cfd_siren_forward_hessian; not selected by cfd_siren_set_compute.  Besides that
+ * entry's errors, CFD_EARG before any launch unless hidden_features is
+ * 32*{1,2,3,4,6,8,12}, num_hidden_layers >= 1, in_coord_features <= 3 and the LDS
+ * staging (2 weight blocks + the FiLM rows) is within 160 KiB. */
+int  cfd_siren_forward_hessian_split(cfd_siren* h, const float* coords, int64_t N, const float* latents, int b,
+                                     const float* xmax, const float* xmin,
+                                     const float* ymax, const float* ymin, int64_t y_stride,
+                                     float* out, float* jac, float* hess, int diag_only,
+                                     void* workspace, size_t ws_bytes, void* stream);
 
 /* Latent-gradient of the Case4 measurement operator (DPS; replaces autograd
  * through Case4Operator.forward -> pass_through_model_batch -> SIRENAutodecoder_film,

@@ -63,6 +63,17 @@ for dims in ((3, 8, 3, 1, 64), (3, 16, 3, 1, 128), (2, 16, 2, 1, 256), (3, 16, 3
     coords = torch.rand(385, dims[0], generator=g).cuda()
     lat = (torch.randn(3, 1, dims[1], generator=g) * 0.5).cuda()
     out[f"siren_ring/{dims}"] = h(nf(coords, lat))
+# the fused value-Jacobian-Hessian decode (K14): d = 1..3, full and diagonal form, odd NB, H = 512
+for dims in ((1, 8, 1, 2, 16), (2, 8, 2, 3, 48), (2, 128, 2, 17, 256), (3, 64, 3, 15, 384), (3, 8, 3, 2, 512)):
+    nf = SIRENAutodecoder_film(*dims)
+    nf.load_state_dict({k: torch.from_numpy(v) for k, v in synth.siren_state_dict(5, *dims).items()})
+    nf.to("cuda")
+    g = torch.Generator().manual_seed(3)
+    coords = torch.rand(77, dims[0], generator=g).cuda()
+    lat = (torch.randn(2, 1, dims[1], generator=g) * 0.5).cuda()
+    for diag in (False, True):
+        o, j, hs = nf.decode_hessian(coords, lat, diag=diag)
+        out[f"siren_hessian/{dims}/{'diag' if diag else 'full'}"] = h(o) + h(j) + h(hs)
 print(json.dumps(out))
 """
 

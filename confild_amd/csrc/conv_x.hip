@@ -40,10 +40,22 @@ __device__ __forceinline__ void split4_mix_x(const f4& x, uint2& hi, uint2& lo) 
     asm("v_fma_mixhi_f16 %0, %1, 1.0, -%2 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(lo.y) : "v"(x[3]), "v"(hi.y));
 }
 
+// 1 / scale of phase ph's pack (a select chain: an indexed kernel argument would
+// be copied to scratch)
+__device__ __forceinline__ float phase_scale(const ConvArgs& a, int ph) {
+    return ph == 0 ? a.ph_scale[0] : ph == 1 ? a.ph_scale[1] : ph == 2 ? a.ph_scale[2] : a.ph_scale[3];
+}
+
 // PF: tiles in flight through registers (1: the next tile; 2: two ahead, two
 // register sets -- for short per-workgroup K ranges where one tile of compute
 // does not cover a load's latency).
-template <int BM, int BN, int WGM, int WGN, int PF = 1>
+// PH: the phase form of an Upsample convolution (nearest 2x, then 3x3): output
+// pixel (2y + py, 2x + px) reads only the 2x2 low-resolution block at
+// (y - 1 + py, x - 1 + px), with the 3x3 taps that fall on one input pre-summed
+// (a.wph / a.wpl: four packs (Cout, 4, Ctot), one per phase (py, px), each with
+// its own scale) -- 4 taps instead of 9.  The M tiles run over the low-resolution
+// pixels of one phase (blockIdx.x = 4 tile + phase) and write with stride 2.
+template <int BM, int BN, int WGM, int WGN, int PF = 1, bool PH = false>
 __global__ __launch_bounds__(64 * WGM * WGN, 1) void conv_x_kernel(ConvArgs a) {
     constexpr int NW = WGM * WGN, NT = 64 * NW;
     constexpr int WTM = BM / WGM, WTN = BN / WGN;   // wave tile
@@ -63,32 +75,42 @@ __global__ __launch_bounds__(64 * WGM * WGN, 1) void conv_x_kernel(ConvArgs a) {
 
     int bx, by, bz;
     xcd_tile(a.xcd, bx, by, bz);
+    const int ph = PH ? bx & 3 : 0, py = ph >> 1, px = ph & 1;
+    if constexpr (PH) bx >>= 2;
     const int m0 = bx * BM, n0 = by * BN;
     const int HWo = a.Hout * a.Wout;
+    // rows of the M dimension: output pixels, or (PH) one phase's low-resolution pixels
+    const int HWm = PH ? a.Hin * a.Win : HWo, Wm = PH ? a.Win : a.Wout, Mm = PH ? a.M >> 2 : a.M;
     const int kq = tid & 7, rsub = tid >> 3;
-    __shared__ int pixtab[9 * BM];   // source pixel of (tap, tile row), -1: padding
+    __shared__ int pixtab[(PH ? 4 : 9) * BM];   // source pixel of (tap, tile row), -1: padding
 
     // buffer resources (32-bit offsets; launch_conv_x checks they fit)
     const int srows = __builtin_amdgcn_readfirstlane(a.Hin * a.Win * (a.M / HWo));   // SGPR: a VGPR descriptor field costs a readfirstlane loop per load
     const __amdgpu_buffer_rsrc_t rs1 = __builtin_amdgcn_make_buffer_rsrc((void*)a.src1, 0, srows * a.C1 * 4, 0x00020000);
     const __amdgpu_buffer_rsrc_t rs2 = __builtin_amdgcn_make_buffer_rsrc(
         (void*)(a.src2 ? (const void*)a.src2 : (const void*)a.src1), 0, a.src2 ? srows * a.C2 * 4 : 0, 0x00020000);
-    const int ntap = a.ks * a.ks, KM = ntap * a.Ctot;
-    const __amdgpu_buffer_rsrc_t rwh = __builtin_amdgcn_make_buffer_rsrc((void*)a.wbf, 0, a.Cout * KM * 2, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rwl = __builtin_amdgcn_make_buffer_rsrc((void*)a.wlo, 0, a.Cout * KM * 2, 0x00020000);
+    const int ntap = PH ? 4 : a.ks * a.ks, KM = ntap * a.Ctot;
+    const char* const wh0 = PH ? (const char*)a.wph + (int64_t)ph * a.Cout * KM * 2 : (const char*)a.wbf;
+    const char* const wl0 = PH ? (const char*)a.wpl + (int64_t)ph * a.Cout * KM * 2 : (const char*)a.wlo;
+    const __amdgpu_buffer_rsrc_t rwh = __builtin_amdgcn_make_buffer_rsrc((void*)wh0, 0, a.Cout * KM * 2, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rwl = __builtin_amdgcn_make_buffer_rsrc((void*)wl0, 0, a.Cout * KM * 2, 0x00020000);
     {
-        const float rhw = 1.0f / (float)HWo, rw = 1.0f / (float)a.Wout;   // fdiv24 (M < 2^24: launch_conv_x)
+        const float rhw = 1.0f / (float)HWm, rw = 1.0f / (float)Wm;   // fdiv24 (M < 2^24: launch_conv_x)
         for (int e = tid; e < ntap * BM; e += NT) {
             const int tap = e / BM, r = e - tap * BM;
-            const int ty = tap_row(tap, a.ks), tx = tap - ty * a.ks;
+            const int ty = PH ? tap >> 1 : tap_row(tap, a.ks), tx = PH ? tap & 1 : tap - ty * a.ks;
             const int m = m0 + r;
             int pix = -1;
-            if (m < a.M) {
-                const int b = fdiv24(m, HWo, rhw), rem = m - b * HWo;
-                const int oy = fdiv24(rem, a.Wout, rw), ox = rem - oy * a.Wout;
+            if (m < Mm) {
+                const int b = fdiv24(m, HWm, rhw), rem = m - b * HWm;
+                const int oy = fdiv24(rem, Wm, rw), ox = rem - oy * Wm;
                 int iy, ix;
                 bool ok;
-                if (a.up) {
+                if constexpr (PH) {
+                    iy = oy - 1 + py + ty;
+                    ix = ox - 1 + px + tx;
+                    ok = iy >= 0 && iy < a.Hin && ix >= 0 && ix < a.Win;
+                } else if (a.up) {
                     iy = oy - a.pad + ty;
                     ix = ox - a.pad + tx;
                     ok = iy >= 0 && iy < 2 * a.Hin && ix >= 0 && ix < 2 * a.Win;
@@ -119,7 +141,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, 1) void conv_x_kernel(ConvArgs a) {
         b_voff[it] = n < a.Cout ? (unsigned)((n * KM + 4 * kq) * 2) : 0x80000000u;
     }
 
-    const int nkt = a.K / 32;
+    const int nkt = KM / 32;
     const int per = (nkt + gridDim.z - 1) / gridDim.z;
     const int kt0 = bz * per;
     const int kt1 = min(nkt, kt0 + per);
@@ -248,17 +270,26 @@ __global__ __launch_bounds__(64 * WGM * WGN, 1) void conv_x_kernel(ConvArgs a) {
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
-        for (int j = 0; j < TN; ++j) acc[i][j] *= a.acc_scale;
+        for (int j = 0; j < TN; ++j) acc[i][j] *= PH ? phase_scale(a, ph) : a.acc_scale;
     const int n_base = n0 + wn * WTN + l32;
     const int m_base = m0 + wm * WTM + 4 * hsel;
+    // output row of M row mm, and its sample
+    auto orow = [&](int mm, int& bb) __attribute__((always_inline)) {
+        bb = mm / HWm;
+        if constexpr (!PH) return mm;
+        const int rem = mm - bb * HWm, y = rem / Wm, x = rem - y * Wm;
+        return (bb * a.Hout + 2 * y + py) * a.Wout + 2 * x + px;
+    };
     if (gridDim.z > 1) {
         float* part = a.part + (int64_t)bz * a.M * a.Cout;
 #pragma unroll
         for (int i = 0; i < TM; ++i)
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
-                const int m = m_base + 32 * i + 8 * (e >> 2) + (e & 3);
-                if (m >= a.M) continue;
+                const int mm = m_base + 32 * i + 8 * (e >> 2) + (e & 3);
+                if (mm >= Mm) continue;
+                int bb;
+                const int m = orow(mm, bb);
 #pragma unroll
                 for (int j = 0; j < TN; ++j) {
                     const int n = n_base + 32 * j;
@@ -275,9 +306,10 @@ __global__ __launch_bounds__(64 * WGM * WGN, 1) void conv_x_kernel(ConvArgs a) {
     for (int i = 0; i < TM; ++i)
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
-            const int m = m_base + 32 * i + 8 * (e >> 2) + (e & 3);
-            if (m >= a.M) continue;
-            const int bb = m / HWo;
+            const int mm = m_base + 32 * i + 8 * (e >> 2) + (e & 3);
+            if (mm >= Mm) continue;
+            int bb;
+            const int m = orow(mm, bb);
 #pragma unroll
             for (int j = 0; j < TN; ++j) {
                 const int n = n_base + 32 * j;
@@ -323,9 +355,15 @@ __global__ __launch_bounds__(64 * WGM * WGN, 1) void conv_x_kernel(ConvArgs a) {
 // copied to LDS as they are -- half the activation bytes, the same bits.
 // BN: output channels per workgroup, 128 (two wave columns) or 64 (one: at small
 // batch twice the workgroups, one wave per SIMD -- the same tiles' sums)
-template <int BM, int TW, bool BF = false, bool SB = false, int BN = 128>
+// PH (split-f16): the phase form of an Upsample convolution, as conv_x_kernel's:
+// the tile is a TR x TW block of LOW-resolution pixels of one phase (py, px)
+// (blockIdx.x = 4 tile + phase), its halo the (TR + 1) x (TW + 1) inputs from
+// (y0 - 1 + py, x0 - 1 + px), 4 steps per chunk on the phase's 2x2 pack, and output
+// pixel (2y + py, 2x + px) is written with stride 2 -- 4/9 of the MFMAs.
+template <int BM, int TW, bool BF = false, bool SB = false, int BN = 128, bool PH = false>
 __global__ __launch_bounds__(BM * (BN / 64), 1) void conv_h_kernel(ConvArgs a) {
     static_assert(!SB || BF, "a bf16 source needs the bf16 kernel");
+    static_assert(!PH || !BF, "the phase form is split-f16 only");
     constexpr unsigned SES = SB ? 2u : 4u;   // source element bytes
     constexpr int WGN = BN / 64, WGM = BM / 64, NTG = 64 * WGM * WGN;   // threads per workgroup
     static_assert(BN == 64 || BN == 128, "K1h: 64 or 128 output channels per workgroup");
@@ -350,7 +388,8 @@ __global__ __launch_bounds__(BM * (BN / 64), 1) void conv_h_kernel(ConvArgs a) {
     // TG taps per step: the bf16 form (one MFMA per product) takes a kernel row of 3
     // taps per step and ring slot, so each barrier is amortised over as many MFMAs as
     // a split-f16 step's (3 per product, one tap); the split form keeps one tap
-    constexpr int TG = BF ? 3 : 1, SPR = 9 / TG;   // taps per step, steps per chunk
+    constexpr int NTAP = PH ? 4 : 9;
+    constexpr int TG = BF ? 3 : 1, SPR = NTAP / TG;   // taps per step, steps per chunk
     constexpr int BPLANE = BN * 64, BSTAGE = PL * BPLANE * TG;
     constexpr int BIT = BN * 4 / NTG;                 // 16-B weight pieces per thread and plane
     constexpr int GBYTES = PL * HPLANE + 2 * BSTAGE;  // the halo + the weight ring
@@ -366,22 +405,31 @@ __global__ __launch_bounds__(BM * (BN / 64), 1) void conv_h_kernel(ConvArgs a) {
     char* const ring = halo + PL * HPLANE;
     int bx, by, bz;
     xcd_tile(a.xcd, bx, by, bz);
+    const int ph = PH ? bx & 3 : 0, py = ph >> 1, px = ph & 1;
+    if constexpr (PH) bx >>= 2;
     const int n0 = by * BN;
-    const int W = a.Wout, HWo = a.Hout * W;
+    // the tiled grid: the output image, or (PH) the low-resolution one
+    const int W = PH ? a.Win : a.Wout, Hh = PH ? a.Hin : a.Hout, HWo = Hh * W;
     // tile bx -> sample, block row, block column (row-major blocks in a sample)
     const int tps = HWo / BM, tpr = W / TW;
     const int bimg = bx / tps, tl = bx - bimg * tps;
     const int y0 = (tl / tpr) * TR, x0 = (tl - (tl / tpr) * tpr) * TW;
-    const int64_t mrow0 = (int64_t)bimg * HWo + (int64_t)y0 * W + x0;   // output pixel of tile position (0, 0)
-    CFD_DASSERT(mrow0 + (int64_t)(TR - 1) * W + TW <= a.M && HWo % BM == 0 && W % TW == 0);
+    // output pixel of tile position (0, 0)
+    const int64_t mrow0 = PH ? ((int64_t)bimg * a.Hout + 2 * y0 + py) * a.Wout + 2 * x0 + px
+                             : (int64_t)bimg * HWo + (int64_t)y0 * W + x0;
+    CFD_DASSERT(mrow0 + (int64_t)(PH ? 2 : 1) * ((int64_t)(TR - 1) * a.Wout + TW - 1) < a.M && HWo % BM == 0 &&
+                W % TW == 0);
 
     // SGPR descriptor fields: a VGPR one costs a readfirstlane loop around every load
-    const int srows = __builtin_amdgcn_readfirstlane(a.Hin * a.Win * (a.M / HWo));
+    const int srows = __builtin_amdgcn_readfirstlane(a.Hin * a.Win * (a.M / (a.Hout * a.Wout)));
     const __amdgpu_buffer_rsrc_t rs1 = __builtin_amdgcn_make_buffer_rsrc((void*)a.src1, 0, srows * a.C1 * SES, 0x00020000);
     const __amdgpu_buffer_rsrc_t rs2 = __builtin_amdgcn_make_buffer_rsrc(
         (void*)(a.src2 ? (const void*)a.src2 : (const void*)a.src1), 0, a.src2 ? srows * a.C2 * SES : 0, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rwh = __builtin_amdgcn_make_buffer_rsrc((void*)a.wbf, 0, a.Cout * 9 * a.Ctot * 2, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rwl = __builtin_amdgcn_make_buffer_rsrc((void*)a.wlo, 0, a.Cout * 9 * a.Ctot * 2, 0x00020000);
+    const int wbytes = a.Cout * NTAP * a.Ctot * 2;   // one plane of the pack (PH: of this phase's)
+    const char* const wh0 = PH ? (const char*)a.wph + (int64_t)ph * wbytes : (const char*)a.wbf;
+    const char* const wl0 = PH ? (const char*)a.wpl + (int64_t)ph * wbytes : (const char*)a.wlo;
+    const __amdgpu_buffer_rsrc_t rwh = __builtin_amdgcn_make_buffer_rsrc((void*)wh0, 0, wbytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rwl = __builtin_amdgcn_make_buffer_rsrc((void*)wl0, 0, wbytes, 0x00020000);
 
     // halo pieces of this thread: halo pixel (gt + it*NTG) >> 3, channel quad gt & 7
     const int kq = gt & 7;
@@ -392,9 +440,10 @@ __global__ __launch_bounds__(BM * (BN / 64), 1) void conv_h_kernel(ConvArgs a) {
         int pix = -1;
         if (hp < NPX) {
             const int hr = hp / HW2, hc = hp - hr * HW2;
-            const int iy = y0 - 1 + hr, ix = x0 - 1 + hc;
-            if (hc < TW + 2 && iy >= 0 && iy < a.Hout && ix >= 0 && ix < W)
-                pix = a.up ? (bimg * a.Hin + (iy >> 1)) * a.Win + (ix >> 1) : (bimg * a.Hin + iy) * a.Win + ix;
+            const int iy = y0 - 1 + hr + py, ix = x0 - 1 + hc + px;
+            // (PH: the last halo row and column are not read)
+            if (hc < TW + (PH ? 1 : 2) && (!PH || hr < TR + 1) && iy >= 0 && iy < Hh && ix >= 0 && ix < W)
+                pix = a.up && !PH ? (bimg * a.Hin + (iy >> 1)) * a.Win + (ix >> 1) : (bimg * a.Hin + iy) * a.Win + ix;
         }
         CFD_DASSERT(pix < srows);
         hpix[it] = pix;
@@ -405,7 +454,7 @@ __global__ __launch_bounds__(BM * (BN / 64), 1) void conv_h_kernel(ConvArgs a) {
 #pragma unroll
     for (int it = 0; it < BIT; ++it) {
         const int n = n0 + (gt >> 2) + it * (NTG / 4);
-        bvoff[it] = n < a.Cout ? (unsigned)((n * 9 * a.Ctot + 8 * bq) * 2) : 0x80000000u;
+        bvoff[it] = n < a.Cout ? (unsigned)((n * NTAP * a.Ctot + 8 * bq) * 2) : 0x80000000u;
     }
 
     // this workgroup's chunks [c0, cend) (its split-K range), one chunk per round
@@ -545,8 +594,8 @@ __global__ __launch_bounds__(BM * (BN / 64), 1) void conv_h_kernel(ConvArgs a) {
                 }
             } else {
             // A fragments: the halo at this tap
-            const int ty = t / 3;
-            const int tofs = ty * HW2 + (t - 3 * ty);
+            const int ty = PH ? t >> 1 : t / 3;
+            const int tofs = ty * HW2 + (PH ? t & 1 : t - 3 * ty);
 #pragma unroll
             for (int s2 = 0; s2 < 2; ++s2) {
                 const int ch = 2 * s2 + hsel;
@@ -602,11 +651,14 @@ __global__ __launch_bounds__(BM * (BN / 64), 1) void conv_h_kernel(ConvArgs a) {
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
-            for (int j = 0; j < 2; ++j) acc[i][j] *= a.acc_scale;
+            for (int j = 0; j < 2; ++j) acc[i][j] *= PH ? phase_scale(a, ph) : a.acc_scale;
     }
     const int n_base = n0 + wn * 64 + l32;
     const int p_base = wm * 64 + 4 * hsel;   // tile position of acc element 0 of block 0
-    auto pix_of = [&](int p) __attribute__((always_inline)) { return mrow0 + (int64_t)(p / TW) * W + (p % TW); };
+    auto pix_of = [&](int p) __attribute__((always_inline)) {
+        if constexpr (PH) return mrow0 + (int64_t)(p / TW) * (2 * a.Wout) + 2 * (p % TW);
+        else return mrow0 + (int64_t)(p / TW) * W + (p % TW);
+    };
     {
         // epilogue through LDS (launch_conv's ldsepi: Cout % 4 == 0, 16-B rows): one
         // 64-pixel wave row of the tile at a time is parked in LDS and leaves as
@@ -708,6 +760,17 @@ int conv_h_tw(const ConvArgs& a) {
     return 0;
 }
 
+// the phase form's K1h tile width (0: the low-resolution image of this Upsample
+// convolution is not tiled by 256-pixel blocks, or it is no Upsample convolution)
+int conv_hp_tw(const ConvArgs& a) {
+    const bool geo = !a.tmode && a.up && a.ks == 3 && a.stride == 1 && a.pad == 1 && a.C1 % 32 == 0 &&
+                     a.C2 % 32 == 0 && a.Hout == 2 * a.Hin && a.Wout == 2 * a.Win && a.M % (a.Hout * a.Wout) == 0;
+    if (!geo) return 0;
+    for (int tw = 64; tw >= 16; tw >>= 1)
+        if (a.Win % tw == 0 && a.Hin % (256 / tw) == 0) return tw;
+    return 0;
+}
+
 int launch_conv_x(const ConvArgs& a, int variant, int splits, hipStream_t st) {
     CFD_REQUIRE(a.wbf && !a.tmode, CFD_ESTATE, "conv_x: split-f16 or bf16 forward only");
     CFD_REQUIRE(a.Ctot % 32 == 0 && a.C1 % 4 == 0 && a.C2 % 4 == 0, CFD_ESHAPE, "conv_x needs channels % 32 == 0");
@@ -762,6 +825,27 @@ int launch_conv_x(const ConvArgs& a, int variant, int splits, hipStream_t st) {
         return splits;
     }
     CFD_REQUIRE(a.wlo, CFD_ESTATE, "internal: K1x runs split-f16 operands only");
+    if (variant >= 24 && variant <= 26) {   // the phase forms of an Upsample convolution
+        CFD_REQUIRE(a.wph && a.wpl && a.up && a.ks == 3 && a.stride == 1 && a.pad == 1 && a.Hout == 2 * a.Hin &&
+                        a.Wout == 2 * a.Win,
+                    CFD_ESTATE, "internal: the phase form needs an Upsample convolution and its phase packs");
+        if (variant == 24) {   // K1h: 256 low-resolution pixels of one phase per workgroup
+            const int tw = conv_hp_tw(a);
+            CFD_REQUIRE(tw > 0, CFD_ESHAPE, "conv_h phase form: a 16/32/64-divisible low-resolution width");
+            const dim3 g = grid(256, 128);   // M / 256 = 4 phases x the low-resolution tiles
+            if (tw == 64) hipLaunchKernelGGL((conv_h_kernel<256, 64, false, false, 128, true>), g, dim3(512), 0, st, a);
+            else if (tw == 32) hipLaunchKernelGGL((conv_h_kernel<256, 32, false, false, 128, true>), g, dim3(512), 0, st, a);
+            else hipLaunchKernelGGL((conv_h_kernel<256, 16, false, false, 128, true>), g, dim3(512), 0, st, a);
+            check_launch("conv_h_kernel (phase)");
+            return splits;
+        }
+        const int bm = variant == 26 ? 256 : 128;
+        const dim3 g(4u * (unsigned)ceil_div(a.M / 4, bm), (unsigned)ceil_div(a.Cout, 128), splits);
+        if (variant == 26) hipLaunchKernelGGL((conv_x_kernel<256, 128, 4, 2, 1, true>), g, dim3(512), 0, st, a);
+        else hipLaunchKernelGGL((conv_x_kernel<128, 128, 2, 2, 1, true>), g, dim3(256), 0, st, a);
+        check_launch("conv_x_kernel (phase)");
+        return splits;
+    }
     switch (variant) {
         case 1: hipLaunchKernelGGL((conv_x_kernel<128, 128, 2, 2>), grid(128, 128), dim3(256), 0, st, a); break;
         case 2: hipLaunchKernelGGL((conv_x_kernel<256, 128, 4, 2>), grid(256, 128), dim3(512), 0, st, a); break;

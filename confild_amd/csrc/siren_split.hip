@@ -292,6 +292,15 @@ __global__ __launch_bounds__(64 * WAVES, CG == 1 ? 2 : 1) void siren_fused_split
     // accumulation.
     int J = 0, slot = 0;
     constexpr int QE = NQ > 1 ? 1 : 0;  // K-chunk of the split / output step
+    if (!NOSYNC) {
+        // the blocks issued above landed (this wave's pieces); the barrier publishes
+        // every wave's pieces before the first read of slot 0.  Layer 0 does not cover
+        // that for the waves that issued nothing: at H = 32 (two pieces, eight waves)
+        // it is one short VALU step, and a wave could read the slot before the DMA
+        // of another wave had written it (non-finite outputs in scattered rows)
+        __builtin_amdgcn_s_waitcnt(vmcnt_imm(0));
+        asm volatile("s_barrier" ::: "memory");
+    }
     for (int layer = 1; layer <= nh; ++layer) {
         const bool last = layer == nh;
         const float m = p.w0f / p.wscale[layer - 1];  // power-of-two scale: exact

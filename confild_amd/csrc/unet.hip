@@ -32,6 +32,11 @@ struct UParam {
     size_t toffset = 0;  // floats into the transposed arena
     float split_inv = 1.f;  // split compute: 1 / s, s = power-of-two scale of this conv weight
     float tsplit_inv = 1.f; // the same for the input-gradient pack
+    // Upsample convolutions (tpack 2) of >= kPhaseMinCout output channels: the forward's phase packs (ConvArgs::wph) at
+    // f16 element poffset of the phase arenas, and 1 / s of each phase's pack
+    bool phase = false;
+    size_t poffset = 0;
+    float psplit_inv[4] = {1.f, 1.f, 1.f, 1.f};
 };
 
 struct ResSpec {
@@ -75,6 +80,9 @@ struct cfd_unet {
     uint16_t* arena_lo = nullptr;
     uint16_t* arena_thi = nullptr;  // split compute: f16 hi / lo parts of the scaled input-gradient packs
     uint16_t* arena_tlo = nullptr;
+    uint16_t* arena_phi = nullptr;  // split compute: the Upsample convolutions' phase packs, f16 hi / lo
+    uint16_t* arena_plo = nullptr;
+    size_t arena_p_elems = 0;
     int compute = CFD_COMPUTE_SPLIT_F16;
     int plan_b = 0;   // the batch the convolution planner tiles for (0: 8); cfd_unet_set_plan_batch
     int tape_mode = CFD_TAPE_INPUT_VJP;   // what the next forward_tape records
@@ -240,6 +248,16 @@ void build(cfd_unet* h) {
         toff += ((p.tpack == 2 ? p.count / 9 * 16 : p.count) + 3) & ~size_t(3);
     }
     h->arena_t_floats = toff;
+    // the forward's phase packs of the Upsample convolutions: 4 phases x (Cout, 4, Cin)
+    size_t poff = 0;
+    for (auto& p : h->params) {
+        // only where the planner can take them (plan_conv: from kPhaseMinCout output channels)
+        if (p.tpack != 2 || p.shape[0] < cfd::kPhaseMinCout) continue;
+        p.phase = true;
+        p.poffset = poff;
+        poff += (p.count / 9 * 16 + 7) & ~size_t(7);   // 16-B aligned packs
+    }
+    h->arena_p_elems = poff;
 }
 
 // bf16 copy (bf16 compute) / f16 hi part (split compute) of a packed conv weight,
@@ -279,6 +297,18 @@ void PTS(const cfd_unet* h, const std::string& key, cfd::ConvArgs* a) {
     a->wbf = h->arena_thi + p.toffset;
     a->wlo = h->arena_tlo + p.toffset;
     a->acc_scale = p.tsplit_inv;
+}
+
+// split compute: the phase packs of an Upsample convolution and their 1 / s into a
+void PP(const cfd_unet* h, const std::string& key, cfd::ConvArgs* a) {
+    if (h->compute != CFD_COMPUTE_SPLIT_F16) return;
+    auto it = h->index.find(key);
+    CFD_REQUIRE(it != h->index.end(), CFD_EKEY, "internal: missing param " + key);
+    const auto& p = h->params[it->second];
+    if (!p.phase) return;
+    a->wph = h->arena_phi + p.poffset;
+    a->wpl = h->arena_plo + p.poffset;
+    for (int ph = 0; ph < 4; ++ph) a->ph_scale[ph] = p.psplit_inv[ph];
 }
 
 const float* PT(const cfd_unet* h, const std::string& key) {
@@ -550,6 +580,7 @@ void run(const cfd_unet* h, const float* x, const int64_t* t, float* eps, int B,
         a.w = P(h, pre + ".weight");
         a.wbf = PB(h, pre + ".weight");
         a.wlo = PL(h, pre + ".weight", &a.acc_scale);
+        if (up) PP(h, pre + ".weight", &a);
         a.bias = P(h, pre + ".bias");
         a.emb = embp;
         a.emb_stride = h->emb_total;
@@ -1187,6 +1218,8 @@ extern "C" int cfd_unet_create(const cfd_unet_cfg* cfg, int device, cfd_unet** o
             CFD_HIP(hipMalloc(&h->arena_lo, sizeof(uint16_t) * std::max<size_t>(h->arena_floats, 4)));
             CFD_HIP(hipMalloc(&h->arena_thi, sizeof(uint16_t) * std::max<size_t>(h->arena_t_floats, 4)));
             CFD_HIP(hipMalloc(&h->arena_tlo, sizeof(uint16_t) * std::max<size_t>(h->arena_t_floats, 4)));
+            CFD_HIP(hipMalloc(&h->arena_phi, sizeof(uint16_t) * std::max<size_t>(h->arena_p_elems, 8)));
+            CFD_HIP(hipMalloc(&h->arena_plo, sizeof(uint16_t) * std::max<size_t>(h->arena_p_elems, 8)));
             const int half = cfg->model_channels / 2;
             // freqs = exp(-ln(10000) * arange(half, fp32) / half) in fp32 (nn.py:129-131)
             std::vector<float> fr(half);
@@ -1216,6 +1249,8 @@ extern "C" void cfd_unet_destroy(cfd_unet* h) {
     (void)hipFree(h->arena_lo);
     (void)hipFree(h->arena_thi);
     (void)hipFree(h->arena_tlo);
+    (void)hipFree(h->arena_phi);
+    (void)hipFree(h->arena_plo);
     (void)hipFree(h->nonfinite);
     (void)hipFree(h->rp_desc);
     (void)hipFree(h->rp_first);
@@ -1341,6 +1376,12 @@ extern "C" int cfd_unet_set_param(cfd_unet* h, const char* key, const float* hos
             }
             CFD_HIP(hipMemcpy(h->arena_thi + p.toffset, thi.data(), pk.size() * 2, hipMemcpyHostToDevice));
             CFD_HIP(hipMemcpy(h->arena_tlo + p.toffset, tlo.data(), pk.size() * 2, hipMemcpyHostToDevice));
+        }
+        if (p.phase) {
+            std::vector<_Float16> phi, plo;
+            cfd::phase_pack_host(host, p.shape[0], p.shape[1], phi, plo, p.psplit_inv);
+            CFD_HIP(hipMemcpy(h->arena_phi + p.poffset, phi.data(), phi.size() * 2, hipMemcpyHostToDevice));
+            CFD_HIP(hipMemcpy(h->arena_plo + p.poffset, plo.data(), plo.size() * 2, hipMemcpyHostToDevice));
         }
         p.set = true;
         ++h->version;
@@ -1559,6 +1600,35 @@ __global__ __launch_bounds__(256) void rp_tpack_kernel(const float* __restrict__
         }
     }
 }
+
+// The phase packs of one Upsample convolution (cfd_unet_set_param's, element for
+// element): blockIdx.y = phase; pass 1 reduces max |tap sum| of each phase into
+// amax4 (zeroed; the bits of a non-negative float order as unsigned), pass 2
+// scales and splits.
+__global__ __launch_bounds__(256) void rp_phase_amax_kernel(const float* __restrict__ w, int64_t ci, int64_t np4,
+                                                            unsigned* __restrict__ amax4) {
+    const int ph = blockIdx.y;
+    float m = 0.f;
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < np4; e += (int64_t)gridDim.x * 256)
+        m = fmaxf(m, fabsf(phase_value(w, ci, ph, e)));
+    __shared__ float r[256];
+    r[threadIdx.x] = m;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (threadIdx.x < s) r[threadIdx.x] = fmaxf(r[threadIdx.x], r[threadIdx.x + s]);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) atomicMax(amax4 + ph, __float_as_uint(r[0]));
+}
+
+__global__ __launch_bounds__(256) void rp_phase_pack_kernel(const float* __restrict__ w, int64_t ci, int64_t np4,
+                                                            const unsigned* __restrict__ amax4,
+                                                            _Float16* __restrict__ phi, _Float16* __restrict__ plo) {
+    const int ph = blockIdx.y;
+    const float s = rp_scale(__uint_as_float(amax4[ph]));
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < np4; e += (int64_t)gridDim.x * 256)
+        rp_split(phase_value(w, ci, ph, e), s, phi, plo, ph * np4 + e);
+}
 }  // namespace cfd
 
 extern "C" int cfd_unet_load_flat(cfd_unet* h, const float* flat, size_t n, void* stream) {
@@ -1614,7 +1684,9 @@ extern "C" int cfd_unet_load_flat(cfd_unet* h, const float* flat, size_t n, void
             CFD_HIP(hipMalloc(&h->rp_desc, sizeof(cfd::RepackDesc) * np));
             CFD_HIP(hipMalloc(&h->rp_first, sizeof(int64_t) * (np + 1)));
             CFD_HIP(hipMalloc(&h->rp_part, sizeof(float) * 2 * blocks));
-            CFD_HIP(hipMalloc(&h->rp_amax, sizeof(float) * 2 * np));
+            size_t nup = 0;
+            for (const auto& p : h->params) nup += p.phase ? 1 : 0;
+            CFD_HIP(hipMalloc(&h->rp_amax, sizeof(float) * (2 * np + 4 * nup)));
             CFD_HIP(hipMemcpy(h->rp_desc, desc.data(), sizeof(cfd::RepackDesc) * np, hipMemcpyHostToDevice));
             CFD_HIP(hipMemcpy(h->rp_first, first.data(), sizeof(int64_t) * (np + 1), hipMemcpyHostToDevice));
             h->rp_blocks = blocks;
@@ -1636,9 +1708,43 @@ extern "C" int cfd_unet_load_flat(cfd_unet* h, const float* flat, size_t n, void
                                (_Float16*)h->arena_tlo);
             cfd::check_launch("rp_tpack_kernel");
         }
-        std::vector<float> amax(2 * (size_t)np);
-        CFD_HIP(hipMemcpyAsync(amax.data(), h->rp_amax, sizeof(float) * 2 * np, hipMemcpyDeviceToHost, st));
+        // the Upsample convolutions' phase packs: two launches each, their four
+        // maxima after the parameters' in rp_amax (2 np floats, then 4 per pack)
+        std::vector<int> ups;
+        for (int k = 0; k < np; ++k)
+            if (h->params[k].phase) ups.push_back(k);
+        unsigned* pamax = (unsigned*)(h->rp_amax + 2 * (size_t)np);
+        if (!ups.empty()) CFD_HIP(hipMemsetAsync(pamax, 0, sizeof(unsigned) * 4 * ups.size(), st));
+        {
+            int64_t src = 0;
+            size_t u = 0;
+            for (int k = 0; k < np; ++k) {
+                const auto& p = h->params[k];
+                if (p.phase) {
+                    const int64_t ci = p.shape[1], np4 = (int64_t)p.count / 9 * 4;
+                    const dim3 g((unsigned)std::min<int64_t>(1024, cfd::ceil_div(np4, 256)), 4);
+                    hipLaunchKernelGGL(cfd::rp_phase_amax_kernel, g, dim3(256), 0, st, flat + src, ci, np4,
+                                       pamax + 4 * u);
+                    cfd::check_launch("rp_phase_amax_kernel");
+                    hipLaunchKernelGGL(cfd::rp_phase_pack_kernel, g, dim3(256), 0, st, flat + src, ci, np4,
+                                       pamax + 4 * u, (_Float16*)h->arena_phi + p.poffset,
+                                       (_Float16*)h->arena_plo + p.poffset);
+                    cfd::check_launch("rp_phase_pack_kernel");
+                    ++u;
+                }
+                src += (int64_t)p.count;
+            }
+        }
+        std::vector<float> amax(2 * (size_t)np + 4 * ups.size());
+        CFD_HIP(hipMemcpyAsync(amax.data(), h->rp_amax, sizeof(float) * amax.size(), hipMemcpyDeviceToHost, st));
         CFD_HIP(hipStreamSynchronize(st));
+        for (size_t u = 0; u < ups.size(); ++u)
+            for (int ph = 0; ph < 4; ++ph) {
+                const float am = amax[2 * (size_t)np + 4 * u + ph];
+                int ex = 0;
+                if (am > 0.f) std::frexp(am, &ex);
+                h->params[ups[u]].psplit_inv[ph] = std::ldexp(1.0f, ex);
+            }
         for (int k = 0; k < np; ++k) {
             auto& p = h->params[k];
             if (p.pack == Pack::Conv1 || p.pack == Pack::Conv3) {
@@ -1654,6 +1760,77 @@ extern "C" int cfd_unet_load_flat(cfd_unet* h, const float* flat, size_t n, void
             p.set = true;
         }
         ++h->version;
+    });
+}
+
+extern "C" int cfd_upsample_conv(const float* x, const float* w_host, const float* bias_host, float* out, int B,
+                                 int H, int W, int Cin, int Cout, int plan_b, int device, int* kx, void* stream) {
+    return cfd::guard([&] {
+        CFD_REQUIRE(x && w_host && bias_host && out, CFD_EARG, "null argument");
+        CFD_REQUIRE(B > 0 && H > 0 && W > 0 && Cin > 0 && Cin % 32 == 0 && Cout > 0 && Cout % 4 == 0 && plan_b >= 0 &&
+                        plan_b <= 64,
+                    CFD_ESHAPE, "upsample conv: Cin % 32 == 0, Cout % 4 == 0, plan batch 0 .. 64");
+        cfd::DeviceGuard dg(device);
+        hipStream_t st = (hipStream_t)stream;
+        const size_t n = (size_t)Cout * Cin * 9;
+        // the 9-tap packs of cfd_unet_set_param, then the phase packs
+        std::vector<float> pk(n);
+        for (int64_t o = 0; o < Cout; ++o)
+            for (int64_t i = 0; i < Cin; ++i)
+                for (int tap = 0; tap < 9; ++tap) pk[(o * 9 + tap) * Cin + i] = w_host[(o * Cin + i) * 9 + tap];
+        float amax = 0.f;
+        for (float v : pk) amax = std::max(amax, std::fabs(v));
+        int ex = 0;
+        if (amax > 0.f) std::frexp(amax, &ex);
+        const float s = std::ldexp(1.0f, -ex);
+        std::vector<_Float16> hi(n), lo(n), phi, plo;
+        for (size_t e = 0; e < n; ++e) {
+            const float v = pk[e] * s;
+            hi[e] = (_Float16)v;
+            lo[e] = (_Float16)(v - (float)hi[e]);
+        }
+        cfd::ConvArgs a{};
+        cfd::phase_pack_host(w_host, Cout, Cin, phi, plo, a.ph_scale);
+        struct Bufs {
+            void* p[7] = {};
+            ~Bufs() { for (void* q : p) (void)hipFree(q); }
+        } d;
+        const size_t bytes[6] = {n * 4, n * 2, n * 2, phi.size() * 2, plo.size() * 2, (size_t)Cout * 4};
+        const void* srcs[6] = {pk.data(), hi.data(), lo.data(), phi.data(), plo.data(), bias_host};
+        for (int k = 0; k < 6; ++k) {
+            CFD_HIP(hipMalloc(&d.p[k], bytes[k]));
+            CFD_HIP(hipMemcpy(d.p[k], srcs[k], bytes[k], hipMemcpyHostToDevice));
+        }
+        a.src1 = x;
+        a.C1 = a.Ctot = Cin;
+        a.w = (const float*)d.p[0];
+        a.wbf = d.p[1];
+        a.wlo = d.p[2];
+        a.wph = d.p[3];
+        a.wpl = d.p[4];
+        a.acc_scale = std::ldexp(1.0f, ex);
+        a.bias = (const float*)d.p[5];
+        a.out = out;
+        a.Hin = H;
+        a.Win = W;
+        a.Hout = 2 * H;
+        a.Wout = 2 * W;
+        a.stride = 1;
+        a.ks = 3;
+        a.pad = 1;
+        a.up = 1;
+        a.Cout = Cout;
+        a.M = B * a.Hout * a.Wout;
+        a.K = 9 * Cin;
+        a.plan_b = plan_b > 0 ? plan_b : 8;
+        const cfd::ConvPlan plan = cfd::plan_conv(a, kSplitPer8);
+        if (plan.splits > 1) {
+            CFD_HIP(hipMalloc(&d.p[6], sizeof(float) * plan.splits * (size_t)a.M * Cout));
+            a.part = (float*)d.p[6];
+        }
+        if (kx) *kx = plan.kx;
+        cfd::launch_conv(a, plan, st);
+        CFD_HIP(hipStreamSynchronize(st));
     });
 }
 

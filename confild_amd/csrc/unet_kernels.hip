@@ -1980,6 +1980,41 @@ ConvPlan plan_conv(const ConvArgs& a, size_t part_cap_floats) {
         while (sp > 1 && (size_t)sp * mn * a.Cout > part_cap_floats) sp /= 2;
         return even_splits(nch, sp);
     };
+#ifndef CFD_NO_UPPHASE
+    // the split-f16 Upsample convolutions (nearest 2x, then 3x3) in their phase
+    // form: four 2x2 convolutions of the low-resolution input on pre-summed taps
+    // (ConvArgs::wph), 4/9 of the MFMAs.  K1h where 256-pixel blocks tile the
+    // low-resolution image, else K1x.  K is 4 Ctot: splits only up to 256
+    // workgroups (a split costs a partial slab written and read).  From 128 output
+    // channels, as K1h and K1x themselves: narrower ones keep their 9-tap K1s plan
+    // (and the bits the pinned small-model tests record).
+    if (a.up && a.wph && a.wpl && a.wbf && a.wlo && !a.tmode && a.ks == 3 && a.stride == 1 && a.pad == 1 &&
+        a.Hout == 2 * a.Hin && a.Wout == 2 * a.Win && a.Cout >= kPhaseMinCout && fits32) {
+        ConvPlan q;
+        q.bn = 128;
+        if (conv_hp_tw(a) > 0) {
+            q.kx = 24;
+            q.bm = 256;
+            q.nw = 8;
+            const int64_t t = ceil_div(mn, 256) * ceil_div(a.Cout, 128);
+            const int nch = a.Ctot / 32;
+            int sp = 1;
+            while (t * sp * 2 <= 256 && sp * 2 <= nch && sp < 16) sp *= 2;
+            while (sp > 1 && (size_t)sp * mn * a.Cout > part_cap_floats) sp /= 2;
+            q.splits = even_splits(nch, sp);
+            return q;
+        }
+        q.kx = mn / 4 >= 2048 ? 26 : 25;
+        q.bm = q.kx == 26 ? 256 : 128;
+        q.nw = q.kx == 26 ? 8 : 4;
+        const int64_t t = 4 * ceil_div(mn / 4, q.bm) * ceil_div(a.Cout, 128);
+        const int nkp = 4 * a.Ctot / 32;
+        q.splits = 1;
+        while (t * q.splits * 2 <= 256 && nkp / (q.splits * 2) >= 4 && q.splits < 32) q.splits *= 2;
+        while (q.splits > 1 && (size_t)q.splits * mn * a.Cout > part_cap_floats) q.splits /= 2;
+        return q;
+    }
+#endif
     // K1hb (conv_x.hip): the bf16-operand 3x3 convolutions (config E) on the halo
     // tiles; the others (8^2, which the 256-pixel tiles do not cover) stay on the
     // K1s bf16 tiles

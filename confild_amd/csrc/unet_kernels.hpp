@@ -1,5 +1,9 @@
 // Launch interface of the U-Net kernels (unet_kernels.hip).
 #pragma once
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
 #include "common.hpp"
 
 namespace cfd {
@@ -51,6 +55,13 @@ struct ConvArgs {
     const void* wbf;     // the same packing in bf16 (config E compute) / f16 hi part (split), or null
     const void* wlo;     // split compute: f16 lo part of the scaled weights, or null
     float acc_scale;     // split compute: 1 / (power-of-two weight scale)
+    // split compute, Upsample convolutions: the phase packs -- four (Cout, 4, Ctot)
+    // packs, one per output parity (py, px), of the 3x3 taps summed over the taps
+    // that read the same low-resolution input; f16 hi / lo parts of each phase's
+    // scaled sums and 1 / scale per phase.  Null: the 9-tap form only.
+    const void* wph;
+    const void* wpl;
+    float ph_scale[4];
     const float* bias;   // (Cout) or null
     const float* emb;    // (B, emb_stride) slice, or null
     const float* res;    // (M, Cout) residual, or null
@@ -82,6 +93,60 @@ struct ConvArgs {
     // depend on the batch it runs in
     int plan_b;
 };
+// the phase form of an Upsample convolution is planned from this many output
+// channels (plan_conv), and its packs are built from there (unet.hip)
+constexpr int kPhaseMinCout = 128;
+
+// Phase packs of an Upsample convolution (nearest 2x, then 3x3 pad 1).  Output
+// pixel (2y + py, 2x + px) reads low-resolution rows y - 1 + py + ty, ty = 0, 1,
+// through the kernel rows  py = 0: {k0}, {k1 + k2};  py = 1: {k0 + k1}, {k2}
+// (columns alike): [lo, hi] of the kernel rows that (parity p, tap t) sums.
+__host__ __device__ inline void phase_taps(int p, int t, int& lo, int& hi) {
+    lo = t == 0 ? 0 : 1 + p;
+    hi = t == 0 ? p : 2;
+}
+// element e of phase ph's (Cout, 4, Cin) pack from the (Cout, Cin, 3, 3) weight:
+// the tap sum in float64 (row-major over the summed taps), rounded once to fp32
+__host__ __device__ inline float phase_value(const float* w, int64_t ci, int ph, int64_t e) {
+    const int64_t i = e % ci, ot = e / ci, o = ot >> 2;
+    const int tap = (int)(ot & 3);
+    int ylo, yhi, xlo, xhi;
+    phase_taps(ph >> 1, tap >> 1, ylo, yhi);
+    phase_taps(ph & 1, tap & 1, xlo, xhi);
+    const float* base = w + (o * ci + i) * 9;
+    double v = 0.0;
+    for (int dy = ylo; dy <= yhi; ++dy)
+        for (int dx = xlo; dx <= xhi; ++dx) v += (double)base[dy * 3 + dx];
+    return (float)v;
+}
+
+// the four phase packs of a (Cout, Cin, 3, 3) weight on the host: per phase the tap
+// sums, scaled by that phase's own power of two (2^-e, e the frexp exponent of the
+// phase's max |sum|) and split hi / lo by the rule of the 9-tap pack; inv: 1 / scale
+inline void phase_pack_host(const float* w, int64_t co, int64_t ci, std::vector<_Float16>& phi,
+                            std::vector<_Float16>& plo, float inv[4]) {
+    const int64_t np4 = co * ci * 4;
+    phi.resize((size_t)np4 * 4);
+    plo.resize((size_t)np4 * 4);
+    std::vector<float> pv((size_t)np4);
+    for (int ph = 0; ph < 4; ++ph) {
+        float amax = 0.f;
+        for (int64_t e = 0; e < np4; ++e) {
+            pv[e] = phase_value(w, ci, ph, e);
+            amax = std::max(amax, std::fabs(pv[e]));
+        }
+        int ex = 0;
+        if (amax > 0.f) std::frexp(amax, &ex);
+        const float sc = std::ldexp(1.0f, -ex);
+        inv[ph] = std::ldexp(1.0f, ex);
+        for (int64_t e = 0; e < np4; ++e) {
+            const float v = pv[e] * sc;
+            phi[ph * np4 + e] = (_Float16)v;
+            plo[ph * np4 + e] = (_Float16)(v - (float)phi[ph * np4 + e]);
+        }
+    }
+}
+
 // development: the timestamp buffer the CFD_STAMPS build's kernels write (null: off)
 void stamps_set(unsigned long long* buf);
 unsigned long long* stamps_buf();
@@ -149,6 +214,7 @@ struct ConvPlan {
     int bm = 128, bn = 128, splits = 1;
     int nw = 4;  // waves per workgroup (8: BM = BN = 128 only)
     int kx = -1; // >= 0: run the K1x kernel variant (conv_x.hip) instead of conv_gemm_kernel;
+                 // 24-26: the phase forms of an Upsample convolution (K1h, K1x 128 / 256 rows);
                  // 40-42: the K1p pointwise tiles (conv_p.hip: 128x128, 64x64, 32x64), never split
     int pf = 1;  // K1s: K tiles in flight through registers (set by launch_conv)
 };
@@ -207,6 +273,7 @@ __device__ __forceinline__ void xcd_tile(int order, int& bx, int& by, int& bz) {
 // 64x64 wave tiles; variant selects the kernel and tile shape
 int launch_conv_x(const ConvArgs& a, int variant, int splits, hipStream_t st);
 int conv_h_tw(const ConvArgs& a);   // K1h tile width for a shape, 0: not applicable
+int conv_hp_tw(const ConvArgs& a);  // the same for the phase form of an Upsample convolution (variant 24)
 // K1p (conv_p.hip): the pointwise split-f16 forward convolutions as a plain GEMM;
 // variant 40 / 41 / 42 selects the 128x128 / 64x64 / 32x64 tile
 bool conv_p_applies(const ConvArgs& a);

@@ -114,6 +114,17 @@ int  cfd_unet_forward(cfd_unet* h, const float* x, const int64_t* t, float* eps,
  * inf / NaN.  Reads the flag accumulated since the previous call (stream-
  * ordered, synchronises `stream`) into *nonfinite and clears it. */
 int  cfd_unet_check_finite(cfd_unet* h, int* nonfinite, void* stream);
+/* NOT PART OF THE STABLE API: a test and development entry (tests/
+ * test_gpu_upsample_phase.py, tools/libdiff.py); it allocates, frees and
+ * synchronises on every call and may change or go without notice.
+ * One Upsample convolution (nearest 2x, then conv3x3 pad 1 with bias) of the
+ * split-f16 compute on its own, planned and launched as the U-Net forward does
+ * at planned batch plan_b (0: 8): x (B, H, W, Cin) and out (B, 2H, 2W, Cout) are
+ * NHWC fp32 on `device`, w_host (Cout, Cin, 3, 3) and bias_host (Cout) on the
+ * host.  *kx receives the planner's kernel variant (24-26: the phase forms).
+ * Packs the weights, runs and synchronises: a test and development entry. */
+int  cfd_upsample_conv(const float* x, const float* w_host, const float* bias_host, float* out, int B, int H,
+                       int W, int Cin, int Cout, int plan_b, int device, int* kx, void* stream);
 
 /* Input-gradient of the U-Net (DPS adjoint; replaces the autograd.grad of
  * grad_and_value through UNetModel.forward, C/src/guided_diffusion/

@@ -12,6 +12,9 @@
 // 32x64) on the 1x1 shapes.  The first line of a shape is the linked library's
 // own plan: link against libconfild_hip_nok1p.so (make VARIANT=nok1p
 // VFLAGS=-DCFD_NO_K1P) for the plans without K1p, reduction launch included.
+// Variants 24 / 25 / 26 are the phase forms of the Upsample convolutions (K1h, K1x
+// 128 / 256 rows) on the `up` shapes; linked against libconfild_hip_noupphase.so
+// (make VARIANT=noupphase VFLAGS=-DCFD_NO_UPPHASE) the first line is the 9-tap plan.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -36,6 +39,7 @@
 namespace cfd {
 int launch_conv_x(const ConvArgs& a, int variant, int splits, hipStream_t st);
 int conv_h_tw(const ConvArgs& a);
+int conv_hp_tw(const ConvArgs& a);
 }
 
 struct Shape {
@@ -89,6 +93,13 @@ static const Shape SHAPES[] = {
     {"C4 96^2 conv 512->256", 1, 96, 96, 512, 0, 256, 3, 1, 0},
     {"C4 48^2 conv 256->256", 1, 48, 48, 256, 0, 256, 3, 1, 0},
     {"C4 48^2 conv 512->256", 1, 48, 48, 512, 0, 256, 3, 1, 0},
+    // config B's three Upsample convolutions, planned batch 8 and 1
+    {"UP 512 (8->16)", 8, 8, 8, 512, 0, 512, 3, 1, 1},
+    {"UP 384 (16->32)", 8, 16, 16, 384, 0, 384, 3, 1, 1},
+    {"UP 256 (32->64)", 8, 32, 32, 256, 0, 256, 3, 1, 1},
+    {"B1 UP 512 (8->16)", 1, 8, 8, 512, 0, 512, 3, 1, 1, 1},
+    {"B1 UP 384 (16->32)", 1, 16, 16, 384, 0, 384, 3, 1, 1, 1},
+    {"B1 UP 256 (32->64)", 1, 32, 32, 256, 0, 256, 3, 1, 1, 1},
 };
 
 static uint16_t f2h(float v) {
@@ -148,6 +159,24 @@ static int bench_main(int argc, char** argv) {
             wh[e] = f2h(v);
             wl[e] = f2h(v - h2f(wh[e]));
         }
+        // Upsample shapes: the four phase packs, by the library's own packing
+        // (cfd::phase_pack_host, unet_kernels.hpp) from the (Cout, Cin, 3, 3) order
+        std::vector<_Float16> ph, pl;
+        float ph_inv[4] = {1.f, 1.f, 1.f, 1.f};
+        if (s.up && s.ks == 3) {
+            std::vector<float> w4((size_t)s.Cout * Ctot * 9);
+            for (size_t o = 0; o < (size_t)s.Cout; ++o)
+                for (size_t i = 0; i < (size_t)Ctot; ++i)
+                    for (int tap = 0; tap < 9; ++tap) w4[(o * Ctot + i) * 9 + tap] = w[(o * 9 + tap) * Ctot + i];
+            cfd::phase_pack_host(w4.data(), s.Cout, Ctot, ph, pl, ph_inv);
+        }
+        _Float16 *dph = nullptr, *dpl = nullptr;
+        if (!ph.empty()) {
+            CK(hipMalloc(&dph, ph.size() * 2));
+            CK(hipMalloc(&dpl, pl.size() * 2));
+            CK(hipMemcpy(dph, ph.data(), ph.size() * 2, hipMemcpyHostToDevice));
+            CK(hipMemcpy(dpl, pl.data(), pl.size() * 2, hipMemcpyHostToDevice));
+        }
         float *d1, *d2, *dw, *db, *out0, *out1, *part;
         uint16_t *dh, *dl;
         CK(hipMalloc(&d1, n1 * 4));
@@ -173,6 +202,9 @@ static int bench_main(int argc, char** argv) {
         a.wbf = dh;
         a.wlo = dl;
         a.acc_scale = 1.f / sc;
+        a.wph = dph;
+        a.wpl = dpl;
+        for (int p = 0; p < 4; ++p) a.ph_scale[p] = ph_inv[p];
         a.bias = db;
         a.out = out0;
         a.part = part;
@@ -218,14 +250,20 @@ static int bench_main(int argc, char** argv) {
             const int BMv_[] = {128, 128, 256, 128, 64, 64, 64, 128, 64, 128}, BNv_[] = {128, 128, 128, 64, 128, 64, 64, 64, 128, 128};
             const int vb = v >= 10 ? 0 : v;
             if (v == 30 && !splits_x) continue;
-            const int BMv = v == 21 ? 128 : v >= 20 ? 256 : BMv_[vb], BNv = BNv_[vb];
+            const int BMv = v == 21 || v == 25 ? 128 : v >= 20 ? 256 : BMv_[vb], BNv = BNv_[vb];
             if ((v == 20 || v == 21) && !cfd::conv_h_tw(a)) continue;
+            const bool phase = v >= 24 && v <= 26;
+            if (phase && (!a.wph || (v == 24 && !cfd::conv_hp_tw(a)))) continue;
             if (v >= 40 && !cfd::conv_p_applies(a)) continue;
             const int64_t tiles = ((M + BMv - 1) / BMv) * ((s.Cout + BNv - 1) / BNv);
             int splits = v >= 40 ? 1 : splits_x;
             if (!splits) {
                 splits = 1;
-                if (v == 20 || v == 21)
+                if (phase)   // the planner's rule for the phase forms: K = 4 Ctot, at most 256 workgroups
+                    while (tiles * splits * 2 <= 256 && (v == 24 ? Ctot / 32 / (splits * 2) >= 1 : 4 * Ctot / 32 / (splits * 2) >= 4) &&
+                           splits < 16)
+                        splits *= 2;
+                else if (v == 20 || v == 21)
                     while (tiles * splits < 256 && Ctot / 32 / (splits * 2) >= (v == 21 ? 4 : 2) && splits < 16) splits *= 2;
                 else
                     while (tiles * splits < 256 && K / 32 / (splits * 2) >= 8 && splits < 16) splits *= 2;
@@ -273,6 +311,8 @@ static int bench_main(int argc, char** argv) {
         CK(hipFree(db));
         CK(hipFree(dh));
         CK(hipFree(dl));
+        CK(hipFree(dph));
+        CK(hipFree(dpl));
         CK(hipFree(out0));
         CK(hipFree(out1));
         CK(hipFree(part));

@@ -3,6 +3,16 @@ runs a fixed set of HIP-path computations in a child process per build
 (CFD_LIB selects the build) and compares the outputs' hashes.
 
     python tools/libdiff.py libconfild_hip_pre.so libconfild_hip.so
+
+The cases named "up/..." run split-f16 Upsample convolutions (every multi-level
+split-f16 U-Net, and cfd_upsample_conv where both builds have it): a build with
+another form of that convolution (the phase form against the 9-tap form) differs
+there at fp32 rounding level, which is reported as max |a - b| / max |a| per case.
+Such a case may differ by at most UP_TOL (1e-5: rounding level of the fp32-accurate
+forward and its adjoint; a wrong kernel is orders above it) and fails the run beyond
+it.  The "up/" cases whose values are not kept for the comparison (parameter
+gradients, the 384^2 model) are listed under `unbounded`.  Every other case must be
+bit-identical.
 """
 from __future__ import annotations
 
@@ -12,17 +22,19 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+UP_TOL = 1e-5   # max |a - b| / max |a| an "up/" case may differ by
 
 CHILD = r"""
-import hashlib, json, sys, torch
+import hashlib, json, sys, torch, numpy as np
 sys.path.insert(0, sys.argv[1])
+vals = {}
 from confild_amd import synth
 from confild_amd.script_util import create_model
 from confild_amd.nf_networks import SIRENAutodecoder_film
 out = {}
 def h(t):
     return hashlib.sha256(t.detach().cpu().contiguous().numpy().tobytes()).hexdigest()[:16]
-cases = [(32, "1,2,3,4", "split_f16", (1, 3)), (64, "", "split_f16", (1, 2, 8)), (128, "", "bf16", (2,)),
+cases = [(16, "2", "split_f16", (3,)), (32, "3", "split_f16", (1,)), (32, "1,2,3,4", "split_f16", (1, 3)), (64, "", "split_f16", (1, 2, 8)), (128, "", "bf16", (2,)),
          (64, "", "fp32", (2,)), (128, "", "split_f16", (1,)), (384, "1,1,2,2,4,4", "split_f16", (1,))]
 for S, mult, comp, Bs in cases:
     m = create_model(image_size=S, num_channels=128, num_res_blocks=2, channel_mult=mult, num_heads=4,
@@ -35,14 +47,23 @@ for S, mult, comp, Bs in cases:
         for B in Bs:
             x = torch.from_numpy(synth.normal(3, f"ld/x{S}", (B, 1, S, S))).cuda()
             t = torch.tensor([999, 500, 3, 250, 700, 10, 900, 60][:B], dtype=torch.int64).cuda()
-            out[f"fwd/{S}/{comp}/pb{pb}/B{B}"] = h(m(x, t))
+            # "up/": the forward runs split-f16 Upsample convolutions
+            up = "up/" if comp == "split_f16" and len(m.channel_mult) > 1 else ""
+            tag = f"{S}/{mult or 'default'}/{comp}/pb{pb}/B{B}"
+            eps = m(x, t)
+            out[f"{up}fwd/{tag}"] = h(eps)
+            if up and S <= 128:
+                vals[f"{up}fwd/{tag}"] = eps.cpu().numpy()
             if comp != "bf16" and S <= 128:
                 m.forward_tape(x, t)
                 d = torch.from_numpy(synth.normal(4, f"ld/d{S}", (B, 1, S, S))).cuda()
-                out[f"vjp/{S}/{comp}/pb{pb}/B{B}"] = h(m.input_vjp(d))
+                g = m.input_vjp(d)
+                out[f"{up}vjp/{tag}"] = h(g)
+                if up:
+                    vals[f"{up}vjp/{tag}"] = g.cpu().numpy()
                 if S <= 64 and B <= 2:
                     m.forward_tape(x, t, for_param_grad=True)
-                    out[f"pgrad/{S}/{comp}/pb{pb}/B{B}"] = h(m.param_grad(d))
+                    out[f"{up}pgrad/{tag}"] = h(m.param_grad(d))
     m.set_plan_batch(0)
 for dims in ((3, 64, 3, 15, 384), (2, 32, 3, 10, 128), (2, 128, 2, 17, 256), (3, 48, 3, 5, 96)):
     nf = SIRENAutodecoder_film(*dims)
@@ -74,22 +95,56 @@ for dims in ((1, 8, 1, 2, 16), (2, 8, 2, 3, 48), (2, 128, 2, 17, 256), (3, 64, 3
     for diag in (False, True):
         o, j, hs = nf.decode_hessian(coords, lat, diag=diag)
         out[f"siren_hessian/{dims}/{'diag' if diag else 'full'}"] = h(o) + h(j) + h(hs)
+# one Upsample convolution on its own (builds that have the entry point)
+from confild_amd import _lib
+import ctypes as C
+if hasattr(_lib.lib(), "cfd_upsample_conv"):
+    for (B, H, W, Ci, Co) in ((8, 8, 8, 512, 512), (8, 16, 16, 384, 384), (2, 32, 32, 256, 256), (3, 4, 4, 96, 96)):
+        x = torch.from_numpy(synth.normal(5, f"ld/ux{H}", (B, H, W, Ci))).cuda()
+        w = torch.from_numpy(synth.normal(5, f"ld/uw{H}", (Co, Ci, 3, 3))) * 0.05
+        b = torch.from_numpy(synth.normal(5, f"ld/ub{H}", (Co,)))
+        o = torch.empty((B, 2 * H, 2 * W, Co), device="cuda")
+        kx = C.c_int(0)
+        _lib.check(_lib.lib().cfd_upsample_conv(_lib.ptr(x), C.c_void_p(w.data_ptr()), C.c_void_p(b.data_ptr()),
+                                                _lib.ptr(o), B, H, W, Ci, Co, 0, 0, C.byref(kx), None), "upconv")
+        out[f"up/conv/{B}x{H}x{W}x{Ci}"] = h(o)
+        vals[f"up/conv/{B}x{H}x{W}x{Ci}"] = o.cpu().numpy()
+np.savez(sys.argv[2], **{k.replace("/", "|"): v for k, v in vals.items()})
 print(json.dumps(out))
 """
 
 
-def run(lib):
+def run(lib, tmp):
     env = dict(os.environ, CFD_LIB=lib)
-    r = subprocess.run([sys.executable, "-c", CHILD, ROOT], capture_output=True, text=True, env=env, timeout=600)
+    vals = os.path.join(tmp, os.path.basename(lib) + ".npz")
+    r = subprocess.run([sys.executable, "-c", CHILD, ROOT, vals], capture_output=True, text=True, env=env,
+                       timeout=900)
     if r.returncode != 0:
         print(r.stderr[-3000:])
         raise SystemExit(1)
-    return json.loads(r.stdout.strip().splitlines()[-1])
+    return json.loads(r.stdout.strip().splitlines()[-1]), vals
 
 
 if __name__ == "__main__":
+    import tempfile
+
+    import numpy as np
+
     a, b = sys.argv[1], sys.argv[2]
-    ra, rb = run(a), run(b)
-    diff = [k for k in ra if ra[k] != rb.get(k)]
-    print(json.dumps({"a": a, "b": b, "cases": len(ra), "differ": diff}))
-    sys.exit(1 if diff else 0)
+    with tempfile.TemporaryDirectory() as tmp:
+        (ra, va), (rb, vb) = run(a, tmp), run(b, tmp)
+        both = [k for k in ra if k in rb]
+        diff = [k for k in both if ra[k] != rb[k]]
+        za, zb = np.load(va), np.load(vb)
+        rel = {}
+        for k in diff:
+            f = k.replace("/", "|")
+            if k.startswith("up/") and f in za.files and f in zb.files:
+                rel[k] = float(np.abs(za[f].astype(np.float64) - zb[f]).max() / np.abs(za[f]).max())
+    bad = [k for k in diff if not k.startswith("up/")]
+    beyond = [k for k, v in rel.items() if not v <= UP_TOL]
+    print(json.dumps({"a": a, "b": b, "cases": len(both), "only_in_one": sorted(set(ra) ^ set(rb)),
+                      "differ_upsample": {k: rel.get(k) for k in diff if k.startswith("up/")},
+                      "unbounded": [k for k in diff if k.startswith("up/") and k not in rel],
+                      "up_tol": UP_TOL, "differ_upsample_beyond_tol": beyond, "differ_other": bad}))
+    sys.exit(1 if bad or beyond else 0)

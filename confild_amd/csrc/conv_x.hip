@@ -19,6 +19,7 @@
 #include <algorithm>
 #include <type_traits>
 
+#include "k1h_lds.hpp"
 #include "unet_kernels.hpp"
 
 namespace cfd {
@@ -323,6 +324,353 @@ __global__ __launch_bounds__(64 * WGM * WGN, 1) void conv_x_kernel(ConvArgs a) {
 }
 
 // ---------------------------------------------------------------------------
+// K1h (below) on v_mfma_f32_16x16x32_f16: the split-f16 forward, SHAPE = 16.  The
+// tile (BM pixels x BN channels, 64 x 64 per wave), the halo, the two-slot weight ring,
+// the grid, the split-K chunk ranges and the step order (chunk, then tap) are the
+// 32x32x16 body's; per step a wave reads 4 A and 4 B fragments of 16 rows x 32
+// channels, hi and lo (16 ds_read_b128, as many as there) and issues 48 MFMAs on
+// 16 accumulators of 4 registers, lo.hi, hi.lo, hi.hi into each.  Lane roles as
+// K1p's (row lane % 16, channels 8 (lane / 16) ..); LDS layout and fragment
+// offsets in k1h_lds.hpp: the taps of a chunk are unrolled, so a fragment read is
+// one of three (two, PH) address registers plus an instruction offset, and a
+// step does no address arithmetic at all -- the ring stage is an offset too (a
+// chunk's step parity is static: rounds are unrolled in pairs where the tap count
+// is odd).  Weight and halo loads are unconditional (a round past the range loads
+// from beyond the descriptors' ends: zeros, no memory access), so every wait
+// before a store is a counted vmcnt.
+template <int V>
+using IC = std::integral_constant<int, V>;
+
+// xcd_tile (unet_kernels.hpp) by value and with selects: its three reference
+// results written on two branches went through 12 B of scratch
+struct Tile3 {
+    int x, y, z;
+};
+__device__ __forceinline__ Tile3 xcd_tile_v(int order) {
+    if (!order) return Tile3{(int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z};
+    const unsigned gx = gridDim.x, gy = gridDim.y, gz = gridDim.z;
+    const unsigned T = gx * gy * gz, L = blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z);
+    const unsigned q = T >> 3, r = T & 7, x = L & 7, sl = L >> 3;
+    const unsigned Lp = x < r ? x * (q + 1) + sl : r * (q + 1) + (x - r) * q + sl;
+    const bool o2 = order == 2;
+    const unsigned d1 = o2 ? gx : gz, d2 = o2 ? gz : gy;   // the fastest and the middle extent
+    const unsigned lo = Lp % d1, rest = Lp / d1, mid = rest % d2, hi = rest / d2;
+    return o2 ? Tile3{(int)lo, (int)hi, (int)mid} : Tile3{(int)hi, (int)mid, (int)lo};
+}
+
+template <int BM, int TW, int BN, bool PH>
+__device__ __forceinline__ void conv_h16_body(const ConvArgs& a) {
+    constexpr int WGN = BN / 64, WGM = BM / 64, NTG = 64 * WGM * WGN;   // threads per workgroup
+    static_assert(BN == 64 || BN == 128, "K1h: 64 or 128 output channels per workgroup");
+    static_assert(TW == 16 || TW == 32 || TW == 64, "K1h: a 16-pixel fragment block lies in one tile row");
+    constexpr int HWD = TW + 2;                       // staged halo columns (LDS row stride: k1h_hws(TW))
+    constexpr int TR = BM / TW, NPX = k1h_npx(BM, TW), NPXD = k1h_npx_staged(BM, TW);
+    constexpr int HPLANE = NPX * 64;                  // one f16 plane of the halo (64 B per pixel)
+    constexpr int HIT = (NPXD * 8 + NTG - 1) / NTG;   // 16-B halo pieces per thread
+    constexpr int NTAP = PH ? 4 : 9, TXN = PH ? 2 : 3;
+    constexpr int BPLANE = BN * 64, BSTAGE = 2 * BPLANE;
+    constexpr int BIT = BN * 4 / NTG;                 // 16-B weight pieces per thread and plane
+    constexpr int GBYTES = 2 * HPLANE + 2 * BSTAGE;   // the halo + the weight ring
+    static_assert(BM % TW == 0 && BIT == 1 && BM % 64 == 0, "tile");
+    static_assert(k1h_a_imm(TW, 3, 2) + HPLANE + 3 * 64 + 64 < 65536, "fragment offsets are instruction offsets");
+    __shared__ __attribute__((aligned(16))) char lds[GBYTES];
+
+    CFD_STAMP(a.stamps, 3, a.seq, 0);
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm = wave / WGN, wn = wave % WGN;
+    const int gt = tid;
+    char* const halo = lds;
+    char* const ring = halo + 2 * HPLANE;
+    const Tile3 wg = xcd_tile_v(a.xcd);
+    int bx = wg.x;
+    const int by = wg.y, bz = wg.z;
+    const int ph = PH ? bx & 3 : 0, py = ph >> 1, px = ph & 1;
+    if constexpr (PH) bx >>= 2;
+    const int n0 = by * BN;
+    const int W = PH ? a.Win : a.Wout, Hh = PH ? a.Hin : a.Hout, HWo = Hh * W;
+    const int tps = HWo / BM, tpr = W / TW;
+    const int bimg = bx / tps, tl = bx - bimg * tps;
+    const int y0 = (tl / tpr) * TR, x0 = (tl - (tl / tpr) * tpr) * TW;
+    const int64_t mrow0 = PH ? ((int64_t)bimg * a.Hout + 2 * y0 + py) * a.Wout + 2 * x0 + px
+                             : (int64_t)bimg * HWo + (int64_t)y0 * W + x0;
+    CFD_DASSERT(mrow0 + (int64_t)(PH ? 2 : 1) * ((int64_t)(TR - 1) * a.Wout + TW - 1) < a.M && HWo % BM == 0 &&
+                W % TW == 0);
+
+    const int srows = __builtin_amdgcn_readfirstlane(a.Hin * a.Win * (a.M / (a.Hout * a.Wout)));
+    const __amdgpu_buffer_rsrc_t rs1 = __builtin_amdgcn_make_buffer_rsrc((void*)a.src1, 0, srows * a.C1 * 4, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs2 = __builtin_amdgcn_make_buffer_rsrc(
+        (void*)(a.src2 ? (const void*)a.src2 : (const void*)a.src1), 0, a.src2 ? srows * a.C2 * 4 : 0, 0x00020000);
+    const int wbytes = a.Cout * NTAP * a.Ctot * 2;   // one plane of the pack (PH: of this phase's)
+    const char* const wh0 = PH ? (const char*)a.wph + (int64_t)ph * wbytes : (const char*)a.wbf;
+    const char* const wl0 = PH ? (const char*)a.wpl + (int64_t)ph * wbytes : (const char*)a.wlo;
+    const __amdgpu_buffer_rsrc_t rwh = __builtin_amdgcn_make_buffer_rsrc((void*)wh0, 0, wbytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rwl = __builtin_amdgcn_make_buffer_rsrc((void*)wl0, 0, wbytes, 0x00020000);
+
+    // halo pieces of this thread: staged pixel (gt + it*NTG) >> 3 of the dense
+    // (TR + 2) x (TW + 2) list, channel quad gt & 7; its source pixel and LDS offset
+    const int kq = gt & 7;
+    int hpix[HIT], hst[HIT];
+#pragma unroll
+    for (int it = 0; it < HIT; ++it) {
+        const int hp = (gt + it * NTG) >> 3;
+        int pix = -1;
+        hst[it] = 0;
+        if (hp < NPXD) {
+            const int hr = hp / HWD, hc = hp - hr * HWD;
+            const int iy = y0 - 1 + hr + py, ix = x0 - 1 + hc + px;
+            // (PH: the last halo row and column are not read)
+            if ((!PH || (hc < TW + 1 && hr < TR + 1)) && iy >= 0 && iy < Hh && ix >= 0 && ix < W)
+                pix = a.up && !PH ? (bimg * a.Hin + (iy >> 1)) * a.Win + (ix >> 1) : (bimg * a.Hin + iy) * a.Win + ix;
+            hst[it] = k1h_stage_off(TW, hp, kq);
+            CFD_DASSERT(hst[it] >= 0 && hst[it] + 8 <= HPLANE);
+        }
+        CFD_DASSERT(pix < srows);
+        hpix[it] = pix;
+    }
+    // weight piece: output channel row gt >> 2, 16-B chunk gt & 3
+    const int bq = gt & 3;
+    const int nrow = n0 + (gt >> 2);
+    const unsigned bvoff = nrow < a.Cout ? (unsigned)((nrow * NTAP * a.Ctot + 8 * bq) * 2) : 0x80000000u;
+    const int wst = k1h_wstage_off(gt >> 2, bq);
+
+    // this workgroup's chunks [c0, cend) (its split-K range), one chunk per round
+    const int nch = a.Ctot / 32;
+    const int per = (nch + gridDim.z - 1) / gridDim.z;
+    const int c0 = bz * per, cend = min(nch, c0 + per);
+    const int nrounds = max(cend - c0, 0);
+
+    f4 rh[HIT];
+    u4 wx_h, wx_l, wy_h, wy_l;   // weight slices two steps deep
+    // chunk c's halo; c == nch (past the range): every offset beyond the descriptor
+    auto load_halo = [&](int c) __attribute__((always_inline)) {
+        const int cb = 32 * c;
+        const bool second = cb >= a.C1;
+        const unsigned csrc = 4u * (unsigned)(second ? a.C2 + 0 : a.C1 + 0);
+        const unsigned cofs = c < nch ? 4u * ((second ? cb - a.C1 : cb) + 4 * kq) : 0x80000000u;
+        if (second) {
+#pragma unroll
+            for (int it = 0; it < HIT; ++it) {
+                const unsigned off = hpix[it] >= 0 ? __umul24((unsigned)hpix[it], csrc) + cofs : 0x80000000u;
+                rh[it] = __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(rs2, off, 0, 0));
+            }
+        } else {
+#pragma unroll
+            for (int it = 0; it < HIT; ++it) {
+                const unsigned off = hpix[it] >= 0 ? __umul24((unsigned)hpix[it], csrc) + cofs : 0x80000000u;
+                rh[it] = __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(rs1, off, 0, 0));
+            }
+        }
+    };
+    auto store_halo = [&]() __attribute__((always_inline)) {
+#pragma unroll
+        for (int it = 0; it < HIT; ++it) {
+            if (gt + it * NTG < NPXD * 8) {
+                uint2 hv, lv;
+                split4_mix_x(rh[it], hv, lv);
+                *(uint2*)(halo + hst[it]) = hv;
+                *(uint2*)(halo + HPLANE + hst[it]) = lv;
+            }
+        }
+    };
+    // the weights of tap t of chunk c (past the range: the last chunk's again, which
+    // nobody reads -- a scalar offset is not bounds-checked, so it stays inside)
+    auto load_w = [&](int c, int t, u4& rbh, u4& rbl) __attribute__((always_inline)) {
+        const int soff = (t * a.Ctot + 32 * min(c, cend - 1)) * 2;
+        rbh = __builtin_bit_cast(u4, __builtin_amdgcn_raw_buffer_load_b128(rwh, bvoff, soff, 0));
+        rbl = __builtin_bit_cast(u4, __builtin_amdgcn_raw_buffer_load_b128(rwl, bvoff, soff, 0));
+    };
+    auto store_w = [&](int stage, const u4& rbh, const u4& rbl) __attribute__((always_inline)) {
+        char* base = ring + stage * BSTAGE + wst;
+        *(u4*)base = rbh;
+        *(u4*)(base + BPLANE) = rbl;
+    };
+
+    f4 acc[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = f4{0.f, 0.f, 0.f, 0.f};
+
+    const int li = lane & 15, g = lane >> 4;
+    // fragment address registers: the halo at column shift tx, and the ring
+    const char* abase[TXN];
+#pragma unroll
+    for (int tx = 0; tx < TXN; ++tx) abase[tx] = halo + k1h_a_base(TW, wm, li, g, tx);
+    const char* const bbase = ring + k1h_b_base(wn, li, g);
+    CFD_DASSERT(k1h_a_base(TW, wm, li, g, TXN - 1) + k1h_a_imm(TW, 3, PH ? 1 : 2) + 16 <= HPLANE);
+
+    // step (round r, tap T) on ring stage Q: prefetch the weights two steps ahead,
+    // the MFMAs, then park the next step's weights (loaded a step ago) in the other
+    // stage.  Every thread runs every step (the barriers are workgroup-wide).
+    auto step = [&](int r, auto tc, auto qc, u4& ldh, u4& ldl, const u4& sth, const u4& stl)
+        __attribute__((always_inline)) {
+        constexpr int T = decltype(tc)::value, Q = decltype(qc)::value;
+        constexpr int ty = PH ? T >> 1 : T / 3, tx = PH ? T & 1 : T - 3 * ty;
+        const int c = c0 + r;
+        load_w(T + 2 < NTAP ? c : c + 1, (T + 2) % NTAP, ldh, ldl);
+        if constexpr (T == 0) load_halo(r + 1 < nrounds ? c + 1 : nch);   // in registers until this chunk's taps are done
+        const char* const ap = abase[tx];
+        const char* const bp = bbase + Q * BSTAGE;
+        h8v fbh[4], fbl[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            fbh[j] = *(const h8v*)(bp + k1h_b_imm(j));
+            fbl[j] = *(const h8v*)(bp + BPLANE + k1h_b_imm(j));
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const h8v fah = *(const h8v*)(ap + k1h_a_imm(TW, i, ty));
+            const h8v fal = *(const h8v*)(ap + HPLANE + k1h_a_imm(TW, i, ty));
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fal, fbh[j], acc[i][j], 0, 0, 0);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fah, fbl[j], acc[i][j], 0, 0, 0);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fah, fbh[j], acc[i][j], 0, 0, 0);
+        }
+        store_w(Q ^ 1, sth, stl);
+        __syncthreads();
+        if constexpr (T == NTAP - 1) {   // every wave is past the last tap of round r
+            store_halo();
+            __syncthreads();
+        }
+        // keep the next step's register-only work behind this barrier
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    // one chunk: its taps in order, the first on ring stage Q0
+    auto round = [&](int r, auto q0c) __attribute__((always_inline)) {
+        constexpr int Q0 = decltype(q0c)::value;
+        auto tap = [&](auto tc) __attribute__((always_inline)) {
+            constexpr int Q = (Q0 + decltype(tc)::value) & 1;
+            if constexpr (Q == 0) step(r, tc, IC<0>{}, wx_h, wx_l, wy_h, wy_l);
+            else step(r, tc, IC<1>{}, wy_h, wy_l, wx_h, wx_l);
+        };
+        tap(IC<0>{}), tap(IC<1>{}), tap(IC<2>{}), tap(IC<3>{});
+        if constexpr (!PH) tap(IC<4>{}), tap(IC<5>{}), tap(IC<6>{}), tap(IC<7>{}), tap(IC<8>{});
+    };
+
+    if (nrounds > 0) {
+        load_w(c0, 0, wx_h, wx_l);
+        load_w(c0, 1, wy_h, wy_l);
+        load_halo(c0);
+        store_w(0, wx_h, wx_l);
+        store_halo();
+        __syncthreads();
+        CFD_STAMP(a.stamps, 3, a.seq, 2);
+        if constexpr (NTAP & 1) {   // an odd tap count: a chunk's ring parity alternates
+            int r = 0;
+            for (; r + 2 <= nrounds; r += 2) {
+                round(r, IC<0>{});
+                round(r + 1, IC<1>{});
+            }
+            if (r < nrounds) round(r, IC<0>{});
+        } else {
+            for (int r = 0; r < nrounds; ++r) round(r, IC<0>{});
+        }
+    }
+
+    CFD_STAMP(a.stamps, 3, a.seq, 3);
+    // undo the split weights' power-of-two scale (exact)
+    const float scl = PH ? phase_scale(a, ph) : a.acc_scale;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] *= scl;
+    // accumulator (i, j), register e: tile pixel wm*64 + 16 i + 4 g + e, channel
+    // n0 + wn*64 + 16 j + li -- 4 consecutive pixels of one channel per lane
+    auto pix_of = [&](int p) __attribute__((always_inline)) {
+        if constexpr (PH) return mrow0 + (int64_t)(p / TW) * (2 * a.Wout) + 2 * (p % TW);
+        else return mrow0 + (int64_t)(p / TW) * W + (p % TW);
+    };
+    // epilogue through LDS (launch_conv's ldsepi), as the 32x32x16 body's: one
+    // 64-pixel wave row of the tile at a time is parked in LDS (k1h_epi) and
+    // leaves as float4 row pieces; the same adds in the same order
+    if (a.ldsepi) {
+        static_assert(64 * BN * 4 <= GBYTES, "epilogue stage fits the LDS");
+        float* stg = (float*)lds;
+        const bool split = gridDim.z > 1;
+        float* dstb = split ? a.part + (int64_t)bz * a.M * a.Cout : a.out;
+        constexpr int Q = BN / 4;   // float4 pieces per staged pixel row
+        __syncthreads();            // every wave is past its last halo / ring read
+        for (int r = 0; r < WGM; ++r) {
+            if (wm == r) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+#pragma unroll
+                        for (int e = 0; e < 4; ++e)
+                            stg[k1h_epi(BN, 16 * i + 4 * g + e, wn * 64 + 16 * j + li)] = acc[i][j][e];
+            }
+            __syncthreads();
+            for (int q = tid; q < 64 * Q; q += NTG) {
+                const int p = q / Q, c = (q - p * Q) * 4;
+                const int n = n0 + c;
+                if (n < a.Cout) {
+                    const int64_t m = pix_of(r * 64 + p);
+                    f4 v = *(const f4*)(stg + k1h_epi(BN, p, c));
+                    if (!split) {
+                        if (a.bias) v = v + *(const f4*)(a.bias + n);
+                        if (a.emb) v = v + *(const f4*)(a.emb + (int64_t)bimg * a.emb_stride + n);
+                        if (a.res) v = *(const f4*)(a.res + m * a.Cout + n) + v;
+                    }
+                    *(f4*)(dstb + m * a.Cout + n) = v;
+                }
+            }
+            __syncthreads();
+        }
+#ifdef CFD_STAMPS
+        __builtin_amdgcn_s_waitcnt(0);
+#endif
+        CFD_STAMP(a.stamps, 3, a.seq, 4);
+        return;
+    }
+    // direct forms: the 16 lanes of a group write 16 consecutive channels of one
+    // pixel, a 64-byte segment
+    const int n_base = n0 + wn * 64 + li;
+    const int p_base = wm * 64 + 4 * g;
+    if (gridDim.z > 1) {
+        float* part = a.part + (int64_t)bz * a.M * a.Cout;
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int64_t m = pix_of(p_base + 16 * i + e);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int n = n_base + 16 * j;
+                    if (n < a.Cout) part[m * a.Cout + n] = acc[i][j][e];
+                }
+            }
+#ifdef CFD_STAMPS
+        __builtin_amdgcn_s_waitcnt(0);
+#endif
+        CFD_STAMP(a.stamps, 3, a.seq, 4);
+        return;
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int64_t m = pix_of(p_base + 16 * i + e);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int n = n_base + 16 * j;
+                if (n >= a.Cout) continue;
+                float v = a.bias ? acc[i][j][e] + a.bias[n] : acc[i][j][e];
+                if (a.emb) v = v + a.emb[(int64_t)bimg * a.emb_stride + n];
+                if (a.res) v = a.res[m * a.Cout + n] + v;
+                a.out[m * a.Cout + n] = v;
+            }
+        }
+#ifdef CFD_STAMPS
+    __builtin_amdgcn_s_waitcnt(0);
+#endif
+    CFD_STAMP(a.stamps, 3, a.seq, 4);
+}
+
+// ---------------------------------------------------------------------------
 // K1h: halo-tiled 3x3 stride-1 convolution (optionally on a nearest-2x
 // upsampled input).  A workgroup's BM output pixels are a TR x TW block
 // (TR = BM / TW rows of TW columns, TW dividing the image width) of one sample;
@@ -360,8 +708,17 @@ __global__ __launch_bounds__(64 * WGM * WGN, 1) void conv_x_kernel(ConvArgs a) {
 // (blockIdx.x = 4 tile + phase), its halo the (TR + 1) x (TW + 1) inputs from
 // (y0 - 1 + py, x0 - 1 + px), 4 steps per chunk on the phase's 2x2 pack, and output
 // pixel (2y + py, 2x + px) is written with stride 2 -- 4/9 of the MFMAs.
-template <int BM, int TW, bool BF = false, bool SB = false, int BN = 128, bool PH = false>
+// SHAPE: the MFMA of the split-f16 form, 32 (v_mfma_f32_32x32x16_f16, the body
+// below: K1hb, and what -DCFD_K1H_MFMA32 keeps everywhere) or 16
+// (v_mfma_f32_16x16x32_f16, conv_h16_body above) -- the same tile, halo, ring,
+// grid, split-K ranges and step order, another fragment layout.
+template <int BM, int TW, bool BF = false, bool SB = false, int BN = 128, bool PH = false, int SHAPE = 32>
 __global__ __launch_bounds__(BM * (BN / 64), 1) void conv_h_kernel(ConvArgs a) {
+    static_assert(SHAPE == 32 || (SHAPE == 16 && !BF && !SB), "K1h: 16x16x32 is the split-f16 form's");
+    if constexpr (SHAPE == 16) {   // (what follows is then unreachable, and compiled away)
+        conv_h16_body<BM, TW, BN, PH>(a);
+        return;
+    }
     static_assert(!SB || BF, "a bf16 source needs the bf16 kernel");
     static_assert(!PH || !BF, "the phase form is split-f16 only");
     constexpr unsigned SES = SB ? 2u : 4u;   // source element bytes
@@ -771,7 +1128,45 @@ int conv_hp_tw(const ConvArgs& a) {
     return 0;
 }
 
-int launch_conv_x(const ConvArgs& a, int variant, int splits, hipStream_t st) {
+// The MFMA shape of a split-f16 K1h launch (variants 20 and 24; K1hb, K1x and the
+// transposed launches never get here).  Forward: 16x16x32 for every tile width,
+// both channel widths and the phase form (tools/convbench variants 32 / 33 and
+// 34 / 35 side by side, three runs, profiles/k1h_mfma_shape.json): per launch
+// x0.86-0.91 at planned batch 8, x0.86-0.96 at planned batch 1 (BN = 64), x0.74-0.83
+// on Case4's unsplit 192^2 / 96^2 / 48^2 launches.  One launch is slower: the phase
+// form at TW = 32 with a single chunk per workgroup (256 channels over 8 splits,
+// planned batch 1), 27.2 us against 26.6-26.8 in all three runs; the phase form
+// at TW = 16 with two chunks per workgroup is faster (22.2-22.8 against 23.8).
+// It keeps the new shape: 0.5 us of a 2.3 ms step, and a rule on the chunks per
+// workgroup would make a sample's bits depend on the split count.  Adjoint (ConvPlan::adjoint: a stride-1 3x3
+// input-gradient, a plain convolution on a mirrored pack that plans as K1h):
+// 32x32x16, the adjoint's kernels and bits as they were.  -DCFD_K1H_MFMA32 keeps
+// 32x32x16 everywhere: the parent's kernels and bits (make VARIANT=k1h32
+// VFLAGS=-DCFD_K1H_MFMA32).
+int k1h_shape(int tw, int bn, bool phase, bool adjoint) {
+    (void)tw, (void)bn, (void)phase;
+#ifdef CFD_K1H_MFMA32
+    (void)adjoint;
+    return 32;
+#else
+    return adjoint ? 32 : 16;
+#endif
+}
+
+template <int BN, bool PH, int SHAPE>
+static void launch_h_(const ConvArgs& a, int tw, dim3 g, hipStream_t st) {
+    const dim3 blk(256 * (BN / 64));
+    if (tw == 64) hipLaunchKernelGGL((conv_h_kernel<256, 64, false, false, BN, PH, SHAPE>), g, blk, 0, st, a);
+    else if (tw == 32) hipLaunchKernelGGL((conv_h_kernel<256, 32, false, false, BN, PH, SHAPE>), g, blk, 0, st, a);
+    else hipLaunchKernelGGL((conv_h_kernel<256, 16, false, false, BN, PH, SHAPE>), g, blk, 0, st, a);
+}
+template <int BN, bool PH>
+static void launch_h(const ConvArgs& a, int tw, int shape, dim3 g, hipStream_t st) {
+    if (shape == 16) launch_h_<BN, PH, 16>(a, tw, g, st);
+    else launch_h_<BN, PH, 32>(a, tw, g, st);
+}
+
+int launch_conv_x(const ConvArgs& a, int variant, int splits, hipStream_t st, bool adjoint) {
     CFD_REQUIRE(a.wbf && !a.tmode, CFD_ESTATE, "conv_x: split-f16 or bf16 forward only");
     CFD_REQUIRE(a.Ctot % 32 == 0 && a.C1 % 4 == 0 && a.C2 % 4 == 0, CFD_ESHAPE, "conv_x needs channels % 32 == 0");
     CFD_REQUIRE(splits == 1 || a.part, CFD_ESTATE, "split-K needs a partial buffer");
@@ -801,41 +1196,36 @@ int launch_conv_x(const ConvArgs& a, int variant, int splits, hipStream_t st) {
         return splits;
     }
     CFD_REQUIRE(!a.src_bf16, CFD_ESTATE, "internal: a bf16 convolution source needs the K1hb kernel");
-    if (variant == 20) {   // K1h: 256-pixel blocks
+    if (variant == 20 || variant == 32 || variant == 33) {   // K1h: 256-pixel blocks
         const int tw = conv_h_tw(a);
-        CFD_REQUIRE(tw > 0, CFD_ESHAPE, "conv_h: 3x3 stride-1 with a 16/32/64-divisible width");
+        CFD_REQUIRE(tw > 0 && a.wlo, CFD_ESHAPE, "conv_h: split-f16 3x3 stride-1 with a 16/32/64-divisible width");
         // small batch: where the 128-channel grid leaves most CUs idle (< 128
         // workgroups of 8 waves, two per SIMD), 64-channel workgroups of 4 waves --
         // twice the workgroups, one wave per SIMD, the same tiles' sums
         // (CFD_CONV_SMALLN=0 keeps 128)
         static const int smalln = smalln_below();
         const dim3 g = grid(256, 128);
-        if ((int64_t)g.x * g.y * g.z < smalln && a.Cout % 64 == 0) {
-            const dim3 g64 = grid(256, 64);
-            if (tw == 64) hipLaunchKernelGGL((conv_h_kernel<256, 64, false, false, 64>), g64, dim3(256), 0, st, a);
-            else if (tw == 32) hipLaunchKernelGGL((conv_h_kernel<256, 32, false, false, 64>), g64, dim3(256), 0, st, a);
-            else hipLaunchKernelGGL((conv_h_kernel<256, 16, false, false, 64>), g64, dim3(256), 0, st, a);
+        const bool n64 = (int64_t)g.x * g.y * g.z < smalln && a.Cout % 64 == 0;
+        const int shape = variant == 20 ? k1h_shape(tw, n64 ? 64 : 128, false, adjoint) : variant == 32 ? 32 : 16;
+        if (n64) {
+            launch_h<64, false>(a, tw, shape, grid(256, 64), st);
             check_launch("conv_h_kernel");
             return splits;
         }
-        if (tw == 64) hipLaunchKernelGGL((conv_h_kernel<256, 64>), g, dim3(512), 0, st, a);
-        else if (tw == 32) hipLaunchKernelGGL((conv_h_kernel<256, 32>), g, dim3(512), 0, st, a);
-        else hipLaunchKernelGGL((conv_h_kernel<256, 16>), g, dim3(512), 0, st, a);
+        launch_h<128, false>(a, tw, shape, g, st);
         check_launch("conv_h_kernel");
         return splits;
     }
     CFD_REQUIRE(a.wlo, CFD_ESTATE, "internal: K1x runs split-f16 operands only");
-    if (variant >= 24 && variant <= 26) {   // the phase forms of an Upsample convolution
+    if ((variant >= 24 && variant <= 26) || variant == 34 || variant == 35) {   // the phase forms of an Upsample convolution
         CFD_REQUIRE(a.wph && a.wpl && a.up && a.ks == 3 && a.stride == 1 && a.pad == 1 && a.Hout == 2 * a.Hin &&
                         a.Wout == 2 * a.Win,
                     CFD_ESTATE, "internal: the phase form needs an Upsample convolution and its phase packs");
-        if (variant == 24) {   // K1h: 256 low-resolution pixels of one phase per workgroup
+        if (variant == 24 || variant == 34 || variant == 35) {   // K1h: 256 low-resolution pixels of one phase per workgroup
             const int tw = conv_hp_tw(a);
             CFD_REQUIRE(tw > 0, CFD_ESHAPE, "conv_h phase form: a 16/32/64-divisible low-resolution width");
             const dim3 g = grid(256, 128);   // M / 256 = 4 phases x the low-resolution tiles
-            if (tw == 64) hipLaunchKernelGGL((conv_h_kernel<256, 64, false, false, 128, true>), g, dim3(512), 0, st, a);
-            else if (tw == 32) hipLaunchKernelGGL((conv_h_kernel<256, 32, false, false, 128, true>), g, dim3(512), 0, st, a);
-            else hipLaunchKernelGGL((conv_h_kernel<256, 16, false, false, 128, true>), g, dim3(512), 0, st, a);
+            launch_h<128, true>(a, tw, variant == 24 ? k1h_shape(tw, 128, true, adjoint) : variant == 34 ? 32 : 16, g, st);
             check_launch("conv_h_kernel (phase)");
             return splits;
         }

@@ -979,7 +979,12 @@ void run_vjp(const cfd_unet* h, const float* d_eps, float* d_x, int B, const std
         a.Cout = cout;
         a.M = B * Hout * Wout;
         a.K = ks * ks * cin;
-        cfd::launch_conv(a, plan_checked(h, a, kSplitCap), st);
+        // a stride-1 3x3 input-gradient with its mirrored pack is a plain convolution
+        // and plans as K1h: marked as the adjoint's, it keeps K1h's 32x32x16 form and
+        // its bits (k1h_shape); the 16x16x32 form is the forward's
+        cfd::ConvPlan plan = plan_checked(h, a, kSplitCap);
+        plan.adjoint = true;
+        cfd::launch_conv(a, plan, st);
     };
     // with_param (training): the GroupNorm's parameter-gradient partials come out of
     // the same statistics pass (GnbArgs::ppart) and are accumulated into dgamma / dbeta
@@ -1829,6 +1834,11 @@ extern "C" int cfd_upsample_conv(const float* x, const float* w_host, const floa
             a.part = (float*)d.p[6];
         }
         if (kx) *kx = plan.kx;
+        static const int conv_log = getenv("CFD_CONV_LOG") ? atoi(getenv("CFD_CONV_LOG")) : 0;
+        if (conv_log)   // development: the plan, as the forward's CONV lines
+            fprintf(stderr, "CONV upsample_conv %dx%d C=%d+%d->%d ks=%d s=%d up=%d M=%d kx=%d bm=%d bn=%d nw=%d splits=%d\n",
+                    a.Hin, a.Win, a.C1, a.C2, a.Cout, a.ks, a.stride, a.up, a.M, plan.kx, plan.bm, plan.bn, plan.nw,
+                    plan.splits);
         cfd::launch_conv(a, plan, st);
         CFD_HIP(hipStreamSynchronize(st));
     });

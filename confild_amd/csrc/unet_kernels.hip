@@ -2184,7 +2184,7 @@ int launch_conv(const ConvArgs& a, const ConvPlan& p0, hipStream_t st, bool defe
         return 1;
     }
     if (p.kx >= 0) {
-        launch_conv_x(a_, p.kx, p.splits, st);
+        launch_conv_x(a_, p.kx, p.splits, st, p.adjoint);
         if (p.splits > 1 && !defer) launch_splitk_reduce(a, p.splits, st);
         return p.splits;
     }

@@ -217,6 +217,10 @@ struct ConvPlan {
                  // 24-26: the phase forms of an Upsample convolution (K1h, K1x 128 / 256 rows);
                  // 40-42: the K1p pointwise tiles (conv_p.hip: 128x128, 64x64, 32x64), never split
     int pf = 1;  // K1s: K tiles in flight through registers (set by launch_conv)
+    // the launch belongs to the adjoint (an input-gradient run as a plain
+    // convolution on a mirrored pack; set by its caller): a K1h plan then keeps the
+    // 32x32x16 form and the adjoint's bits (k1h_shape)
+    bool adjoint = false;
 };
 
 constexpr int kGnMaxChunks = 512;
@@ -269,11 +273,17 @@ __device__ __forceinline__ void xcd_tile(int order, int& bx, int& by, int& bz) {
         bx = Lp / (gz * gy);
     }
 }
-// K1x / K1h (conv_x.hip): split-f16 forward convolutions on 32x32x16 MFMAs with
-// 64x64 wave tiles; variant selects the kernel and tile shape
-int launch_conv_x(const ConvArgs& a, int variant, int splits, hipStream_t st);
+// K1x / K1h (conv_x.hip): split-f16 forward convolutions with 64x64 wave tiles
+// (K1x and K1hb on 32x32x16 MFMAs, K1h on the shape k1h_shape gives); variant
+// selects the kernel and tile shape; adjoint: ConvPlan::adjoint
+int launch_conv_x(const ConvArgs& a, int variant, int splits, hipStream_t st, bool adjoint = false);
 int conv_h_tw(const ConvArgs& a);   // K1h tile width for a shape, 0: not applicable
 int conv_hp_tw(const ConvArgs& a);  // the same for the phase form of an Upsample convolution (variant 24)
+// the MFMA shape (32: 32x32x16, 16: 16x16x32) of a split-f16 K1h launch of tile
+// width tw, bn channels per workgroup, 9-tap or phase form, forward or adjoint
+// (variants 20 / 24; the development variants 32 / 33 and 34 / 35 force a shape:
+// tools/convbench)
+int k1h_shape(int tw, int bn, bool phase, bool adjoint);
 // K1p (conv_p.hip): the pointwise split-f16 forward convolutions as a plain GEMM;
 // variant 40 / 41 / 42 selects the 128x128 / 64x64 / 32x64 tile
 bool conv_p_applies(const ConvArgs& a);

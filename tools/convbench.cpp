@@ -15,6 +15,11 @@
 // Variants 24 / 25 / 26 are the phase forms of the Upsample convolutions (K1h, K1x
 // 128 / 256 rows) on the `up` shapes; linked against libconfild_hip_noupphase.so
 // (make VARIANT=noupphase VFLAGS=-DCFD_NO_UPPHASE) the first line is the 9-tap plan.
+// Variants 32 / 33 are K1h on 32x32x16 / 16x16x32 MFMAs and 34 / 35 its phase form
+// on the two, each at the library's own plan (splits) and with launch_conv's
+// epilogue and workgroup order, so one binary times the two shapes side by side:
+//   CX_SHAPES="K1H " build/convbench 32 33 34 35
+// (the config-B halo-tile shapes at planned batch 8 and 1).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -37,7 +42,6 @@
     } while (0)
 
 namespace cfd {
-int launch_conv_x(const ConvArgs& a, int variant, int splits, hipStream_t st);
 int conv_h_tw(const ConvArgs& a);
 int conv_hp_tw(const ConvArgs& a);
 }
@@ -100,6 +104,23 @@ static const Shape SHAPES[] = {
     {"B1 UP 512 (8->16)", 1, 8, 8, 512, 0, 512, 3, 1, 1, 1},
     {"B1 UP 384 (16->32)", 1, 16, 16, 384, 0, 384, 3, 1, 1, 1},
     {"B1 UP 256 (32->64)", 1, 32, 32, 256, 0, 256, 3, 1, 1, 1},
+    // config B's K1h shapes (variants 32 - 35), planned batch 8 and 1
+    {"K1H 64^2 128->128", 8, 64, 64, 128, 0, 128, 3, 1, 0},
+    {"K1H 64^2 128+128->128", 8, 64, 64, 128, 128, 128, 3, 1, 0},
+    {"K1H 32^2 256->256", 8, 32, 32, 256, 0, 256, 3, 1, 0},
+    {"K1H 32^2 256+256->256", 8, 32, 32, 256, 256, 256, 3, 1, 0},
+    {"K1H 16^2 384->384", 8, 16, 16, 384, 0, 384, 3, 1, 0},
+    {"K1H 16^2 384+384->384", 8, 16, 16, 384, 384, 384, 3, 1, 0},
+    {"K1H UP 384 (16->32)", 8, 16, 16, 384, 0, 384, 3, 1, 1},
+    {"K1H UP 256 (32->64)", 8, 32, 32, 256, 0, 256, 3, 1, 1},
+    {"K1H B1 64^2 128->128", 1, 64, 64, 128, 0, 128, 3, 1, 0, 1},
+    {"K1H B1 64^2 128+128->128", 1, 64, 64, 128, 128, 128, 3, 1, 0, 1},
+    {"K1H B1 32^2 256->256", 1, 32, 32, 256, 0, 256, 3, 1, 0, 1},
+    {"K1H B1 32^2 256+256->256", 1, 32, 32, 256, 256, 256, 3, 1, 0, 1},
+    {"K1H B1 16^2 384->384", 1, 16, 16, 384, 0, 384, 3, 1, 0, 1},
+    {"K1H B1 16^2 384+384->384", 1, 16, 16, 384, 384, 384, 3, 1, 0, 1},
+    {"K1H B1 UP 384 (16->32)", 1, 16, 16, 384, 0, 384, 3, 1, 1, 1},
+    {"K1H B1 UP 256 (32->64)", 1, 32, 32, 256, 0, 256, 3, 1, 1, 1},
 };
 
 static uint16_t f2h(float v) {
@@ -252,11 +273,13 @@ static int bench_main(int argc, char** argv) {
             if (v == 30 && !splits_x) continue;
             const int BMv = v == 21 || v == 25 ? 128 : v >= 20 ? 256 : BMv_[vb], BNv = BNv_[vb];
             if ((v == 20 || v == 21) && !cfd::conv_h_tw(a)) continue;
+            const bool shape_ab = v >= 32 && v <= 35;   // K1h at the library's plan, one MFMA shape forced
+            if (shape_ab && p.kx != (v < 34 ? 20 : 24)) continue;
             const bool phase = v >= 24 && v <= 26;
             if (phase && (!a.wph || (v == 24 && !cfd::conv_hp_tw(a)))) continue;
             if (v >= 40 && !cfd::conv_p_applies(a)) continue;
             const int64_t tiles = ((M + BMv - 1) / BMv) * ((s.Cout + BNv - 1) / BNv);
-            int splits = v >= 40 ? 1 : splits_x;
+            int splits = v >= 40 ? 1 : shape_ab ? p.splits : splits_x;
             if (!splits) {
                 splits = 1;
                 if (phase)   // the planner's rule for the phase forms: K = 4 Ctot, at most 256 workgroups
@@ -271,6 +294,10 @@ static int bench_main(int argc, char** argv) {
             cfd::ConvArgs b = a;
             b.out = out1;
             b.xcd = 1;
+            if (shape_ab) {   // as launch_conv sets them
+                b.ldsepi = s.Cout % 4 == 0;
+                b.xcd = Hout * Wout <= 256 ? 2 : 1;
+            }
             // variant 30: the shipped K1s tiles of the planner's choice at CX_SPLITS splits
             cfd::ConvPlan p30 = p;
             p30.splits = splits;

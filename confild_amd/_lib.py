@@ -162,6 +162,14 @@ _SIGS = {
                                        C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                        C.c_size_t, C.c_void_p]),
     "cfd_siren_dense_set_form": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "cfd_siren_jdense_plan": (C.c_int, [C.POINTER(SirenCfg), C.c_int64, C.c_int, C.c_int, C.c_size_t,
+                                        C.POINTER(C.c_size_t), C.POINTER(C.c_int64), C.POINTER(C.c_int)]),
+    "cfd_siren_jdense_workspace_bytes": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_size_t,
+                                                   C.POINTER(C.c_size_t)]),
+    "cfd_siren_jdense_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int,
+                                        C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]),
     "cfd_siren_train_workspace_bytes": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_size_t)]),
     "cfd_siren_train_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int,
                                        C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

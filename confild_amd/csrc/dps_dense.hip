@@ -521,6 +521,34 @@ void launch_dense(int NB, const DenseArgs& a, int rows, int mode, hipStream_t st
 }
 
 }  // namespace
+
+// the chunk and tail steps shared with the dense Jacobian adjoint (K16, siren_jdense.hip)
+void launch_dense_slab_sum(const float* items, float* part, int n_items, int per, int64_t nf, int rows, int slabs,
+                           hipStream_t st) {
+    hipLaunchKernelGGL(dense_slab_sum, dim3((unsigned)ceil_div(nf, 256), rows, slabs), dim3(256), 0, st, items, part,
+                       n_items, per, nf);
+    check_launch("dense_slab_sum");
+}
+
+void launch_dense_accum(const float* part, const double* sspart, float* D, double* rowss, int rows, int slabs,
+                        int64_t nf, hipStream_t st) {
+    hipLaunchKernelGGL(dense_accum_kernel, dim3((unsigned)ceil_div((int64_t)rows * nf, 256)), dim3(256), 0, st, part,
+                       sspart, D, rowss, rows, slabs, nf);
+    check_launch("dense_accum_kernel");
+}
+
+void dense_tail(const cfd_siren* h, const float* D, const double* rowss, float* norm, float* g_latents, float* gpart,
+                int R, int T, hipStream_t st) {
+    const int L = h->cfg.in_latent_features, B = R / T;
+    const int nf = (h->cfg.num_hidden_layers + 1) * h->cfg.hidden_features;
+    hipLaunchKernelGGL(dense_norm_kernel, dim3((unsigned)ceil_div(B, 64)), dim3(64), 0, st, rowss, norm, B, T);
+    check_launch("dense_norm_kernel");
+    launch_gemm_f32(false, D, nf, h->V, L, nullptr, g_latents, L, R, L, nf, st, gpart);
+    hipLaunchKernelGGL(dense_scale_kernel, dim3((unsigned)ceil_div((int64_t)R * L, 256)), dim3(256), 0, st, g_latents,
+                       norm, (int64_t)R * L, (int64_t)T * L);
+    check_launch("dense_scale_kernel");
+}
+
 }  // namespace cfd
 
 extern "C" int cfd_siren_dense_plan(const cfd_siren_cfg* cfg, int64_t N, int R, size_t budget, int bwd_form,
@@ -669,23 +697,11 @@ extern "C" int cfd_siren_dense_grad(cfd_siren* h, const float* coords, int64_t N
                 }
                 if (delta || split) {
                     const int n_items = delta ? nc : (int)cfd::ceil_div(nc, 16), per = delta ? cfd::kSlab : cfd::kSlab / 16;
-                    hipLaunchKernelGGL(cfd::dense_slab_sum, dim3((unsigned)cfd::ceil_div(nf, 256), rows, slabs),
-                                       dim3(256), 0, st, base + pl.delta, base + pl.part, n_items, per, nf);
-                    cfd::check_launch("dense_slab_sum");
+                    cfd::launch_dense_slab_sum(base + pl.delta, base + pl.part, n_items, per, nf, rows, slabs, st);
                 }
-                hipLaunchKernelGGL(cfd::dense_accum_kernel, dim3((unsigned)cfd::ceil_div((int64_t)rows * nf, 256)),
-                                   dim3(256), 0, st, base + pl.part, sspart, D + (int64_t)r0 * nf, rowss + r0, rows,
-                                   slabs, nf);
-                cfd::check_launch("dense_accum_kernel");
+                cfd::launch_dense_accum(base + pl.part, sspart, D + (int64_t)r0 * nf, rowss + r0, rows, slabs, nf, st);
             }
         }
-        const int B = R / T;
-        hipLaunchKernelGGL(cfd::dense_norm_kernel, dim3((unsigned)cfd::ceil_div(B, 64)), dim3(64), 0, st, rowss, norm, B,
-                           T);
-        cfd::check_launch("dense_norm_kernel");
-        cfd::launch_gemm_f32(false, D, (int)nf, h->V, L, nullptr, g_latents, L, R, L, (int)nf, st, base + pl.gpart);
-        hipLaunchKernelGGL(cfd::dense_scale_kernel, dim3((unsigned)cfd::ceil_div((int64_t)R * L, 256)), dim3(256), 0,
-                           st, g_latents, norm, (int64_t)R * L, (int64_t)T * L);
-        cfd::check_launch("dense_scale_kernel");
+        cfd::dense_tail(h, D, rowss, norm, g_latents, base + pl.gpart, R, T, st);
     });
 }

@@ -160,5 +160,15 @@ void film_vectors(const cfd_siren* h, const float* latents, int b, float* film, 
 // g_z (R, L) from the tape deltas (R, Ns, nh+1, H); D: R (nh+1) H floats and the GEMM's split-K partials
 void latent_grad_from_delta(const cfd_siren* h, const float* delta, float* D, int64_t Ns, int R, float* g_latents,
                             hipStream_t st);
+// chunk and tail steps of the dense adjoints (dps_dense.hip; K16 in siren_jdense.hip shares them):
+// part[row][slab] = the slab's `per` items of (rows, n_items, nf) in item order;
+// D[row] += the chunk's slab partials in slab order and rowss[row] += sspart[row][slab] likewise;
+// norm[b] = sqrt(the sample's row sums in row order), g_latents = (D . V) / norm (zero at norm 0)
+void launch_dense_slab_sum(const float* items, float* part, int n_items, int per, int64_t nf, int rows, int slabs,
+                           hipStream_t st);
+void launch_dense_accum(const float* part, const double* sspart, float* D, double* rowss, int rows, int slabs,
+                        int64_t nf, hipStream_t st);
+void dense_tail(const cfd_siren* h, const float* D, const double* rowss, float* norm, float* g_latents, float* gpart,
+                int R, int T, hipStream_t st);
 
 }  // namespace cfd

@@ -35,6 +35,12 @@ Case4 sequence on the Jacobian tape, readings (T, Ns, M):
 
 A ``mask`` keyword with it raises NotImplementedError (a zero weight row does that).
 
+DenseStencilOperator ('dense_stencil': the same stencils at every point of a whole
+field -- a measured vorticity field, divergence-free guidance at all collocation
+points) takes the dense branch instead, readings (T, N, M) and masks of (N, M) tables:
+
+    g_z, norm = cfd_siren_jdense_grad(unnorm(x0), y, weights, mask) (bounded workspace)
+
 InpaintingOperator (A(x0) = mask * x0 on the latent image, measurements.py:40-56)
 needs no decoder: the three SIREN lines and cfd_dps_latent_grad become
 
@@ -77,7 +83,8 @@ from ..gaussian_diffusion import (KNOWN_COUNTER, LossType, ModelMeanType, ModelV
                                   broadcast_rows, check_model_range, fresh_seed, get_named_beta_schedule)
 from ..respace import SpacedDiffusion, space_timesteps
 from .condition_methods import Identity, PosteriorSampling
-from .measurements import _STENCIL_MASK, Case4Operator, InpaintingOperator, SensorStencilOperator
+from .measurements import (_STENCIL_MASK, Case4Operator, DenseStencilOperator, InpaintingOperator,
+                           SensorStencilOperator)
 
 __SAMPLER__ = {}
 
@@ -261,8 +268,9 @@ class _GuidedSampler(SpacedDiffusion):
             if kw.get("mask") is not None:
                 raise NotImplementedError(_STENCIL_MASK)
             return None
-        return _mask_tables(kw.get("mask"), op, x.shape[0], x.shape[2], op.coords.shape[0], op.model.out_features,
-                            x.device)
+        # tables of (N, c) values, or of (N, M) readings for 'dense_stencil'
+        width = op.readings if isinstance(op, DenseStencilOperator) else op.model.out_features
+        return _mask_tables(kw.get("mask"), op, x.shape[0], x.shape[2], op.coords.shape[0], width, x.device)
 
     def _update(self, sample, g_dir, g_unet, scale, t, seed, counter, offset, kn, nz2):
         """The step's last call: cfd_dps_update, or with known rows (``kn`` a _Known)
@@ -284,7 +292,7 @@ class _GuidedSampler(SpacedDiffusion):
     def _guided_step(self, model, x, i, measurement, method, noise, seed, counter, sample_offset, dist_out,
                      mask=None, kn=None, known_noise=None):
         """x (B, 1, T, L) contiguous fp32 on the GPU; updated in place for 'ps'.
-        mask: None or the (1 | T | B*T, N, c) device tables of _mask_tables.
+        mask: None or the (1 | T | B*T, N, c) device tables of _mask_tables ((N, M) for 'dense_stencil').
         kn: None or the _Known rows; known_noise: their normals (x's shape) or None."""
         dev = x.device
         if dev.type != "cuda":
@@ -335,7 +343,9 @@ class _GuidedSampler(SpacedDiffusion):
             g_unet = model.input_vjp(d_eps)
             img = self._update(sample, g_dir, g_unet, float(method.scale), t, seed, counter, offset, kn, nz2)
             return img, x0, sample
-        y = measurement.to(device=dev, dtype=torch.float32).contiguous()
+        # a 'dense_stencil' measurement may be None: a zero target (e.g. zero divergence)
+        dense_zero = measurement is None and isinstance(op, DenseStencilOperator)
+        y = None if dense_zero else measurement.to(device=dev, dtype=torch.float32).contiguous()
         vmax, vmin = op._bounds()
         if n % vmax.numel():
             raise ValueError("latent max/min do not tile the latent")
@@ -355,7 +365,8 @@ class _GuidedSampler(SpacedDiffusion):
             _, g_out, g_jac, _ = op.residual(out, jac, y, B, dist_out)
             gz = op.vjp(g_out, g_jac)                                    # (B*T, L)
         else:
-            # a dense or masked measurement: norm and latent gradient in bounded memory
+            # a dense or masked measurement (values: K12; 'dense_stencil' readings: K16):
+            # norm and latent gradient in bounded memory
             gz, norms = op.dense_grad(x0, y, mask, self.dense_budget)
             dist_out.copy_(norms)
         d_eps = torch.empty_like(x)

@@ -386,8 +386,100 @@ class SensorStencilOperator(_SirenFieldOperator):
         return self.model.jac_tape_vjp(g_out, g_jac)
 
 
+class _StencilReadings:
+    """A (R, n, M) of cfd_dps_residual_linear for point batches [n0, n1) of an operator's
+    stencils.  The call also wants a target and writes the residual's gradients: a
+    zero target and two scratch buffers, allocated once for the largest batch."""
+
+    def __init__(self, op, R, step):
+        c, d, dev = op.model.out_features, op.model.in_coord_features, op.coords.device
+        self.op, self.R, self.M, self.c, self.d = op, R, op.readings, c, d
+        self.zero = torch.zeros(R * step * self.M, dtype=torch.float32, device=dev)
+        self.A = torch.empty(R * step * self.M, dtype=torch.float32, device=dev)
+        self.g_out = torch.empty(R * step * c, dtype=torch.float32, device=dev) if op.wv is not None else None
+        self.g_jac = torch.empty(R * step * c * d, dtype=torch.float32, device=dev) if op.wj is not None else None
+        self.norm = torch.empty(1, dtype=torch.float32, device=dev)
+
+    def __call__(self, out, jac, n0, n1):
+        op, n = self.op, n1 - n0
+        wv = op.wv[n0:n1].contiguous() if op.wv_per_sensor else op.wv
+        wj = op.wj[n0:n1].contiguous() if op.wj_per_sensor else op.wj
+        out, jac = out.contiguous(), jac.contiguous()
+        _lib.check(_lib.lib().cfd_dps_residual_linear(
+            _lib.ptr(self.zero), 0, _lib.ptr(out), _lib.ptr(jac), _lib.ptr(wv), int(op.wv_per_sensor), _lib.ptr(wj),
+            int(op.wj_per_sensor), _lib.ptr(self.g_out), _lib.ptr(self.g_jac), _lib.ptr(self.norm), _lib.ptr(self.A),
+            n, self.M, self.c, self.d, self.R, 1, _lib.stream_of(out.device)), "cfd_dps_residual_linear")
+        return self.A[:self.R * n * self.M].reshape(self.R, n, self.M)
+
+
 _STENCIL_MASK = ("the 'sensor_stencil' operator takes no mask keyword: switch a sensor or a reading off with a "
                  "zero weight row")
+
+
+@register_operator(name="dense_stencil")
+class DenseStencilOperator(_SirenFieldOperator):
+    """SensorStencilOperator's readings at every point of a whole field (no reference
+    counterpart): M linear stencils per point on the decoded value and its exact
+    coordinate Jacobian,
+
+        A[r, n, m] = sum_o wv[n, m, o] out[r, n, o] + sum_{o,k} wj[n, m, o, k] jac[r, n, o, k]
+
+    with ``value_weights`` (M, c) or per point (N, M, c) and ``jac_weights`` (M, c, d) or
+    (N, M, c, d).  Where 'sensor_stencil' keeps the whole Jacobian tape in memory, the DPS
+    sampler runs this operator's adjoint in bounded memory (``dense_grad``:
+    cfd_siren_jdense_grad), so N may be the whole mesh: a measured
+    vorticity field, divergence-free guidance at every collocation point (a zero
+    measurement), or, with per-point weights, value sensors at a few points and a
+    derivative reading at all of them.  A ``mask`` keyword (tables of (N, M)) works as
+    for case2 / case3.  It has no forward_tape / vjp."""
+
+    _name = "DenseStencil"
+
+    # SensorStencilOperator's constructor files, weight arrays and weight checks
+    __init__ = SensorStencilOperator.__init__
+    _set_weights = SensorStencilOperator._set_weights
+
+    @classmethod
+    def from_parts(cls, device, coords, x_normalizer, y_normalizer, model, max_val, min_val, batch_size=384,
+                   value_weights=None, jac_weights=None):
+        op = super().from_parts(device, coords, x_normalizer, y_normalizer, model, max_val, min_val, batch_size)
+        op._set_weights(value_weights, jac_weights)
+        return op
+
+    def _y_normalizer_at(self, n0, n1):
+        """The y normaliser of points [n0, n1): a per-point (N, c) table is sliced."""
+        yn, N, c = self.y_normalizer, self.coords.shape[0], self.model.out_features
+        if yn is None or yn.method != "-11" or yn.params[0].numel() != N * c or N == 1:
+            return yn
+        return Normalizer_ts(method="-11", dim=0, params=tuple(p.reshape(N, c)[n0:n1] for p in yn.params[:2]))
+
+    def forward(self, data, mask=None, **kwargs):
+        """(s, 1, t, l) latents in [-1, 1] -> (s*t, N, M) readings (times ``mask``):
+        decode_jacobian and the stencil contraction (cfd_dps_residual_linear's A) in
+        batches of ``batch_size`` points, so the Jacobian of the whole field is never
+        held at once."""
+        _require_gpu(data)
+        rows = self._rows(data)
+        R, N, M = rows.shape[0], self.coords.shape[0], self.readings
+        A = torch.empty((R, N, M), dtype=torch.float32, device=rows.device)
+        step = max(1, min(N, int(self.batch_size)))
+        readings = _StencilReadings(self, R, step)
+        for n0 in range(0, N, step):
+            n1 = min(N, n0 + step)
+            with torch.no_grad():
+                out, jac = self.model.decode_jacobian(self.coords[n0:n1], rows[:, None], self.x_normalizer,
+                                                      self._y_normalizer_at(n0, n1))
+            A[:, n0:n1] = readings(out, jac, n0, n1)
+        return A if mask is None else torch.as_tensor(mask).to(device=A.device, dtype=A.dtype) * A
+
+    # -- adjoint used by the DPS sampler ----------------------------------------
+    def dense_grad(self, data, measurement, mask=None, budget=None):
+        """(g_z (s*t, l), norms (s)): ||y - mask * forward(data)|| per sample and its gradient
+        w.r.t. the un-normalised latent rows, in bounded memory
+        (SIRENAutodecoder_film.jac_dense_grad).  ``measurement`` None: a zero target."""
+        _require_gpu(data)
+        return self.model.jac_dense_grad(self.coords, self._rows(data), data.shape[2], measurement, self.wv, self.wj,
+                                         mask, self.x_normalizer, self.y_normalizer, budget)
 
 
 # =============

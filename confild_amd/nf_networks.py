@@ -531,6 +531,76 @@ class SIRENAutodecoder_film(nn.Module):
                                             ws.numel(), budget, _lib.stream_of(dev)), "cfd_siren_dense_grad")
         return gz, norms
 
+    # -- dense derivative measurements (K16: cfd_siren_jdense_grad) ----------------------
+    def jac_dense_grad(self, coords, latents, rows_per_sample, y, value_weights=None, jac_weights=None, mask=None,
+                       x_normalizer=None, y_normalizer=None, budget=None):
+        """dense_grad() for linear stencils on the value and the exact coordinate
+        Jacobian at every point: with (out, jac) = decode_jacobian(coords, latents) and
+            A[r, n, m] = sum_o wv[n, m, o] out[r, n, o] + sum_{o,k} wj[n, m, o, k] jac[r, n, o, k],
+            norms[b] = || y - mask * A ||_2,   g_z = d norms / d latents
+        in bounded memory.  value_weights: (M, c) or per point (N, M, c); jac_weights:
+        (M, c, d) or (N, M, c, d); at least one.  y: None (a zero target), (T, N, M) shared
+        by the samples or (R, N, M); mask: None, (N, M), (T, N, M) or (R, N, M).  budget,
+        normalisers and the result as dense_grad; always the exact fp32 chain.
+        Returns (g_z (R, L), norms (R / T))."""
+        d, L, c = self.in_coord_features, self.in_latent_features, self.out_features
+        dev = latents.device
+        if dev.type != "cuda":
+            raise _lib.CfdError("SIREN jac_dense_grad needs GPU tensors (the HIP path has no CPU fallback)")
+        cf = coords.reshape(-1, d).to(device=dev, dtype=torch.float32).contiguous()
+        lat = latents.detach().reshape(-1, L).to(torch.float32).contiguous()
+        N, R, T = cf.shape[0], lat.shape[0], int(rows_per_sample)
+        if T < 1 or R % T:
+            raise ValueError(f"rows_per_sample {T} does not divide the {R} latent rows")
+        cf, xmax, xmin, ymax, ymin, ystride, post = self._norm_args(cf, N, dev, x_normalizer, y_normalizer)
+        if post is not None or (x_normalizer is not None and xmax is None):
+            raise NotImplementedError("the SIREN Jacobian adjoint fuses '-11' normalisers only")
+        if value_weights is None and jac_weights is None:
+            raise ValueError("jac_dense_grad needs value_weights, jac_weights or both")
+        M, w, per_point = None, [None, None], [0, 0]
+        for i, (name, t, tail) in enumerate((("value_weights", value_weights, (c,)),
+                                             ("jac_weights", jac_weights, (c, d)))):
+            if t is None:
+                continue
+            t = torch.as_tensor(t).detach().to(device=dev, dtype=torch.float32).contiguous()
+            if t.dim() == 1 + len(tail) and tuple(t.shape[1:]) == tail:
+                m = t.shape[0]
+            elif t.dim() == 2 + len(tail) and t.shape[0] == N and tuple(t.shape[2:]) == tail:
+                m, per_point[i] = t.shape[1], 1
+            else:
+                raise ValueError(f"{name} of shape {tuple(t.shape)} is neither {('M',) + tail} nor "
+                                 f"{(N, 'M') + tail}")
+            if m < 1 or (M is not None and m != M):
+                raise ValueError(f"{name} has {m} readings per point, expected {M if M is not None else 'at least 1'}")
+            M, w[i] = m, t
+        yv, y_rows = None, 0
+        if y is not None:
+            yv = y.detach().to(device=dev, dtype=torch.float32).contiguous()
+            if yv.numel() not in (T * N * M, R * N * M):
+                raise ValueError(f"measurement of {yv.numel()} values matches neither one sample ({T * N * M}) nor "
+                                 f"the batch ({R * N * M})")
+            y_rows = yv.numel() // (N * M)
+        mv, mask_rows = None, 0
+        if mask is not None:
+            mv = mask.detach().to(device=dev, dtype=torch.float32).contiguous()
+            mask_rows = mv.numel() // (N * M)
+            if mv.numel() != mask_rows * N * M or mask_rows not in (1, T, R):
+                raise ValueError(f"mask of {mv.numel()} values is not 1, {T} or {R} tables of ({N}, {M})")
+        h, lib = self._handle(dev), _lib.load()
+        budget = 0 if budget is None else int(budget)
+        n = C.c_size_t()
+        _lib.check(lib.cfd_siren_jdense_workspace_bytes(h, N, R, M, budget, C.byref(n)), "siren jdense workspace")
+        ws = torch.empty(max(n.value, 16), dtype=torch.uint8, device=dev)
+        self.dense_workspace_bytes = n.value   # what the last call allocated
+        gz = torch.empty((R, L), dtype=torch.float32, device=dev)
+        norms = torch.empty((R // T,), dtype=torch.float32, device=dev)
+        _lib.check(lib.cfd_siren_jdense_grad(h, _lib.ptr(cf), N, _lib.ptr(lat), R, T, _lib.ptr(xmax), _lib.ptr(xmin),
+                                             _lib.ptr(ymax), _lib.ptr(ymin), ystride, _lib.ptr(w[0]), per_point[0],
+                                             _lib.ptr(w[1]), per_point[1], M, _lib.ptr(yv), y_rows, _lib.ptr(mv),
+                                             mask_rows, _lib.ptr(gz), _lib.ptr(norms), _lib.ptr(ws), ws.numel(),
+                                             budget, _lib.stream_of(dev)), "cfd_siren_jdense_grad")
+        return gz, norms
+
     # -- training (K10: cfd_siren_train_grad; the loop is confild_amd.cnf_train) ----
     def param_keys(self):
         """Parameter keys in the library's flat-gradient order (cfd_siren_param_info)."""

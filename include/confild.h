@@ -558,6 +558,41 @@ int  cfd_siren_dense_grad(cfd_siren* h, const float* coords, int64_t N,
 #define CFD_DENSE_COMPUTE_F32   1
 int  cfd_siren_dense_set_form(cfd_siren* h, int bwd_form, int compute_form);
 
+/* Dense derivative measurements (K16; no reference counterpart): the dense adjoint
+ * above for linear stencils on the value and the exact coordinate Jacobian at every
+ * one of N points, M readings per point,
+ *   A[r, n, m] = sum_o wv[n, m, o] out[r, n, o] + sum_{o,k} wj[n, m, o, k] jac[r, n, o, k]
+ * (out, jac as cfd_siren_forward_jacobian gives them, physical units):
+ *   norm[b]   = || y - m (.) A ||_2 over the sample's T N M readings;
+ *   g_latents (R, L) = d norm / d latents (zero where the norm is zero).
+ *   wv:   (M, c), or with wv_per_point (N, M, c); wj: (M, c, d) or (N, M, c, d).
+ *         Either may be NULL (no such term), not both.
+ *   y:    NULL (a zero target) or y_rows tables of (N, M), y_rows = rows_per_sample
+ *         or R; row r reads table r % y_rows.
+ *   mask: NULL (all ones) or mask_rows in {1, rows_per_sample, R} tables of (N, M).
+ * Chunks, row blocks, budget and determinism as cfd_siren_dense_grad: K15's chain
+ * (cfd_siren_jtape_*) on row-aligned tiles, its tape kept for one chunk only
+ * ((1 + d) rows nc (nh+1) H floats) and u-bar summed on chip, no atomics; g_latents
+ * and norm do not depend on budget, row blocking or the samples sharing the call.
+ * Always the exact fp32 chain, whatever cfd_siren_set_compute chose.
+ * CFD_EARG before any launch: a NULL required pointer, both weights NULL, M < 1,
+ * N < 1, R < 1, rows_per_sample not dividing R, y_rows / mask_rows outside the sets
+ * above, in_coord_features > 3, a workspace even one byte short, a budget too small
+ * for one slab of one row; CFD_ESHAPE: in_latent_features % 4 or (nh+1) H % 16.
+ * cfd_siren_jdense_plan: the planner from a configuration alone (no device). */
+int  cfd_siren_jdense_plan(const cfd_siren_cfg* cfg, int64_t N, int R, int M, size_t budget,
+                           size_t* bytes, int64_t* chunk_points, int* block_rows);
+int  cfd_siren_jdense_workspace_bytes(const cfd_siren* h, int64_t N, int R, int M, size_t budget, size_t* bytes);
+int  cfd_siren_jdense_grad(cfd_siren* h, const float* coords, int64_t N,
+                           const float* latents, int R, int rows_per_sample,
+                           const float* xmax, const float* xmin,
+                           const float* ymax, const float* ymin, int64_t y_stride,
+                           const float* wv, int wv_per_point, const float* wj, int wj_per_point, int M,
+                           const float* y, int y_rows,
+                           const float* mask, int mask_rows,
+                           float* g_latents, float* norm,
+                           void* workspace, size_t ws_bytes, size_t budget, void* stream);
+
 /* ------------------------------------------------------------------------ */
 /* CNF autodecoder training (K10; N/scripts/train.py:334-416 _single_trainer:  */
 /* model(coords, latents(idx)) -> MSELoss -> loss.backward(), Adam steps).     */

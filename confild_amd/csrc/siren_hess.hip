@@ -25,8 +25,6 @@
 // computed for the same argument.  A group lies inside a 16-lane row, and the four
 // arrive by ds_bpermute_b32 (the LDS crossbar, no LDS memory).  Value and tangent columns evaluate K13's expressions;
 // the second-order update is one fixed fmaf sequence, the same in every instantiation.
-#include <algorithm>
-
 #include "siren_hess.hpp"
 
 namespace cfd {
@@ -103,12 +101,8 @@ __global__ __launch_bounds__(64 * WAVES, NB <= 24 ? 2 : 1) void siren_hess_fused
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const f4 w = *(const f4*)(w0s + 4 * (16 * q + 4 * g + r));
-            float a = cn[0] * w[0];
-#pragma unroll
-            for (int k = 1; k < 3; ++k)
-                if (k < d) a = fmaf(cn[k], w[k], a);
             // sine in the value and second-order columns, cosine in the tangent columns
-            const float sc = hess_sincos_role(w0f * (a + fv[r]), !tangent);
+            const float sc = sincos_role(w0f * layer0_preact(cn, w, d, fv[r]), !tangent);
             const float wk = ck == 0 ? w[0] : ck == 1 ? w[1] : w[2];
             const float wl = cl == 0 ? w[0] : cl == 1 ? w[1] : w[2];
             const float sv = second_order(w0f, w0sq, sc, 0.0f, 0.0f, wk * sk, wl * sl);
@@ -151,7 +145,7 @@ __global__ __launch_bounds__(64 * WAVES, NB <= 24 ? 2 : 1) void siren_hess_fused
                 // one reduction and one polynomial per lane: the sine in the value and
                 // second-order columns, the cosine in the tangent columns, from where the
                 // second-order columns fetch it (tangent 0 of the group has it for the same x)
-                const float sc = hess_sincos_role(x, !tangent);
+                const float sc = sincos_role(x, !tangent);
                 const float cu = lane_value(src_c, sc);
                 const float sv = second_order(w0f, w0sq, sc, cu, av, ak, al);
                 X[q][r] = value ? sc : tangent ? (w0f * sc) * av : second ? sv : 0.0f;
@@ -169,41 +163,15 @@ __global__ __launch_bounds__(64 * WAVES, NB <= 24 ? 2 : 1) void siren_hess_fused
 
 namespace {
 
-template <int NB, int RS>
-void launch_hess_nb(const cfd_siren* h, cfd::SirenHessArgs a, hipStream_t st) {
-    // K13's workgroup shapes: 8 waves (2 per SIMD) share one weight stream; NB = 32
-    // runs 4 waves (1 per SIMD, the overflow in AGPRs)
-    constexpr int WAVES = NB <= 24 ? 8 : 4, TILE = (16 / RS) * WAVES;
-    const int H = NB * 16;
-    const size_t lds = (size_t)(2 * NB * 256 + (h->cfg.num_hidden_layers + 1) * H + 4 * H) * sizeof(float);
-    const void* fn = (const void*)cfd::siren_hess_fused<NB, RS, WAVES>;
-    CFD_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const int64_t tiles = cfd::ceil_div(a.N, TILE);
-    CFD_REQUIRE(tiles <= 0x7fffffff, CFD_EARG, "too many query points for one call");
-    for (int64_t b0 = 0; b0 < a.b; b0 += 65535) {
-        a.b0 = b0;
-        const int nb = (int)std::min<int64_t>(65535, a.b - b0);
-        hipLaunchKernelGGL((cfd::siren_hess_fused<NB, RS, WAVES>), dim3((unsigned)tiles, nb), dim3(64 * WAVES), lds, st,
-                           a);
-        cfd::check_launch("siren_hess_fused");
-    }
-}
-
 template <int RS>
 void launch_hess(const cfd_siren* h, const cfd::SirenHessArgs& a, hipStream_t st) {
-    switch (h->NB) {
-        case 1: return launch_hess_nb<1, RS>(h, a, st);
-        case 2: return launch_hess_nb<2, RS>(h, a, st);
-        case 3: return launch_hess_nb<3, RS>(h, a, st);
-        case 4: return launch_hess_nb<4, RS>(h, a, st);
-        case 6: return launch_hess_nb<6, RS>(h, a, st);
-        case 8: return launch_hess_nb<8, RS>(h, a, st);
-        case 12: return launch_hess_nb<12, RS>(h, a, st);
-        case 16: return launch_hess_nb<16, RS>(h, a, st);
-        case 24: return launch_hess_nb<24, RS>(h, a, st);
-        case 32: return launch_hess_nb<32, RS>(h, a, st);
-        default: throw cfd::Error{CFD_EARG, "hidden_features must be 16*{1,2,3,4,6,8,12,16,24,32}"};
-    }
+    cfd::dispatch_nb(h->NB, [&](auto nbc) {
+        // K13's workgroup shapes: 8 waves (2 per SIMD) share one weight stream; NB = 32
+        // runs 4 waves (1 per SIMD, the overflow in AGPRs)
+        constexpr int NB = decltype(nbc)::value, WAVES = NB <= 24 ? 8 : 4;
+        cfd::launch_decode(cfd::siren_hess_fused<NB, RS, WAVES>, "siren_hess_fused", a, NB, (16 / RS) * WAVES, WAVES,
+                           st);
+    });
 }
 
 }  // namespace
@@ -217,44 +185,17 @@ extern "C" int cfd_siren_forward_hessian(cfd_siren* h, const float* coords, int6
                                          int64_t y_stride, float* out, float* jac, float* hess, int diag_only, void* ws,
                                          size_t ws_bytes, void* stream) {
     return cfd::guard([&] {
-        CFD_REQUIRE(h && coords && latents && hess, CFD_EARG, "null argument");
-        CFD_REQUIRE(N >= 1 && b >= 1, CFD_EARG, "empty decode");
-        CFD_REQUIRE((xmax == nullptr) == (xmin == nullptr), CFD_EARG, "xmax/xmin must both be set or both NULL");
-        CFD_REQUIRE((ymax == nullptr) == (ymin == nullptr), CFD_EARG, "ymax/ymin must both be set or both NULL");
-        const int d = h->cfg.in_coord_features;
-        CFD_REQUIRE(d <= 3, CFD_EARG,
-                    "cfd_siren_forward_hessian: in_coord_features must be 1..3 (the value, tangent and second-order "
-                    "chains of a point share 16 MFMA columns)");
-        size_t need = 0;
-        cfd_siren_hessian_workspace_bytes(h, b, &need);
-        CFD_REQUIRE(ws && ws_bytes >= need, CFD_EARG, "workspace too small");
+        cfd::decode_check("cfd_siren_forward_hessian",
+                          "the value, tangent and second-order chains of a point share 16 MFMA columns", h, coords, N,
+                          latents, b, xmax, xmin, ymax, ymin, hess);
         auto st = (hipStream_t)stream;
-        float* film = (float*)ws;
-        cfd::film_vectors(h, latents, b, film, st);
-        cfd::SirenHessArgs a{};
-        a.w0 = h->w0;
-        a.wimg = h->wimg;
-        a.wout = h->wout;
-        a.bout = h->bout;
-        a.film = film;
-        a.coords = coords;
-        a.xmax = xmax;
-        a.xmin = xmin;
-        a.ymax = ymax;
-        a.ymin = ymin;
-        a.out = out;
-        a.jac = jac;
+        auto a = cfd::decode_args<cfd::SirenHessArgs>(h, coords, N, latents, b, xmax, xmin, ymax, ymin, y_stride, out,
+                                                      jac, ws, ws_bytes, st);
         a.hess = hess;
-        a.N = N;
-        a.ystride = y_stride;
-        a.b = b;
-        a.d = d;
-        a.c = h->cfg.out_features;
-        a.nh = h->cfg.num_hidden_layers;
         a.diag = diag_only != 0;
-        a.w0f = h->cfg.w0;
         // always the exact fp32 chain, whatever the handle's compute mode.  d <= 2 runs
         // the full form for both outputs; d = 3 has a diagonal form of 8 columns per point
+        const int d = a.d;
         const bool full = d < 3 || !a.diag;
         a.nsec = full ? d * (d + 1) / 2 : d;
         if (d == 1)

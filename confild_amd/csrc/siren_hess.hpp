@@ -1,23 +1,11 @@
 // Shared pieces of the fused value-Jacobian-Hessian decodes: K14 (siren_hess.hip,
 // exact fp32 MFMA chain) and K14s (siren_hess_split.hip, split-f16 MFMA chain).
 #pragma once
-#include "siren.hpp"
+#include "siren_jac.hpp"
 
 namespace cfd {
 
-struct SirenHessArgs {
-    const float* w0;      // (H, d)
-    const float* wimg;    // hidden weight image (as SirenArgs)
-    const float* wout;    // (c, H)
-    const float* bout;    // (c)
-    const float* film;    // (b, nh+1, H)
-    const float* coords;  // (N, d)
-    const float* xmax;
-    const float* xmin;
-    const float* ymax;
-    const float* ymin;
-    float* out;           // (b, N, c) or null
-    float* jac;           // (b, N, c, d) or null
+struct SirenHessArgs : SirenDecodeArgs {
     float* hess;          // (b, N, c, d, d), or (b, N, c, d) with diag
     int64_t N;
     int64_t ystride;
@@ -32,30 +20,6 @@ struct SirenHessArgs {
 struct SirenHessSplitArgs : SirenHessArgs {
     const float* wscale;
 };
-
-// sin(x) where value is set, cos(x) elsewhere, from one reduction (K13's sincos_role,
-// bit for bit sin_cw / cos_cw of common.hpp): "x - qq * (pi/2 split)" with qq = 2q
-// (sine) or the odd q' (cosine), one shared polynomial; sin: negate for odd q
-// (qq & 2), cos: negate unless qq & 2.
-__device__ __forceinline__ float hess_sincos_role(float x, bool value) {
-    const float t = fmaf(x, 0.318309886183790671538f, value ? 0.0f : -0.5f);
-    const float qq = fmaf(2.0f, rintf(t), value ? 0.0f : 1.0f);
-    float r = fmaf(qq, -1.5703125f, x);
-    r = fmaf(qq, -0.00048351287841796875f, r);
-    r = fmaf(qq, -3.13855707645416259765625e-07f, r);
-    r = fmaf(qq, -6.077100628276710381e-11f, r);
-    const float s = r * r;
-    float u = 2.6083159809786593541503e-06f;
-    u = fmaf(u, s, -0.0001981069071916863322258f);
-    u = fmaf(u, s, 0.00833307858556509017944336f);
-    u = fmaf(u, s, -0.166666597127914428710938f);
-    const float y = fmaf(s, u * r, r);
-    const bool neg = (((unsigned)(int)qq & 2u) != 0u) == value;
-    const float v = __uint_as_float(__float_as_uint(y) ^ (neg ? (1u << 31) : 0u));
-    const float xr = x * 0.159154943091895335768f;
-    const float hw = value ? __builtin_amdgcn_sinf(xr) : __builtin_amdgcn_cosf(xr);
-    return fabsf(x) < 39000.0f ? v : hw;
-}
 
 // v of the lane whose byte address (4 * lane) is addr: ds_bpermute_b32, no LDS memory
 __device__ __forceinline__ float lane_value(int addr, float v) {

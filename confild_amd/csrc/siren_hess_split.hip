@@ -29,10 +29,7 @@
 // point's index nor its neighbours; scaling coordinate k by a power of two moves the
 // exponents by integers and no carried bit.  The op sequence is the same in every
 // instantiation: the diagonal form is the full form's diagonal to the bit.
-#include <algorithm>
-
 #include "siren_hess.hpp"
-#include "siren_jac.hpp"
 
 namespace cfd {
 
@@ -134,12 +131,8 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 8 ? 2 : 1) void siren_hess_spl
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const f4 w = *(const f4*)(w0s + 4 * (16 * q + 4 * g + r));
-            float a = cn[0] * w[0];
-#pragma unroll
-            for (int k = 1; k < 3; ++k)
-                if (k < d) a = fmaf(cn[k], w[k], a);
             // sine in the value and second-order columns, cosine in the tangent columns
-            const float sc = hess_sincos_role(w0f * (a + fv[r]), !tangent);
+            const float sc = sincos_role(w0f * layer0_preact(cn, w, d, fv[r]), !tangent);
             const float wk = ck == 0 ? w[0] : ck == 1 ? w[1] : w[2];
             const float wl = cl == 0 ? w[0] : cl == 1 ? w[1] : w[2];
             const float sv = second_order(w0f, w0sq, sc, 0.0f, 0.0f, wk * sk, wl * sl);
@@ -168,33 +161,11 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 8 ? 2 : 1) void siren_hess_spl
         E = F;
         static_for<NB>([&](auto jc) {
             constexpr int j = decltype(jc)::value;
-            if (J + 1 < nblocks) siren_issue_block<NB, WAVES>(p.wimg, J + 1, wbuf + ((J + 1) & 1) * BLK, wave, lane);
-            const float* wb = wbuf + (J & 1) * BLK;
-            f4 a = *(const f4*)(film + layer * H + 16 * j + 4 * g);
-            if (!value) a = f4{0.f, 0.f, 0.f, 0.f};
-            // chunk q + 1's A fragments are read under chunk q's MFMAs (K13s)
-            jh8 FH = *(const jh8*)(wb + lane * 4);
-            jh8 FL = *(const jh8*)(wb + 256 + lane * 4);
-            static_for<NQ>([&](auto qc) {
-                constexpr int q = decltype(qc)::value;
-                jh8 FH1 = FH, FL1 = FL;
-                if constexpr (q + 1 < NQ) {
-                    FH1 = *(const jh8*)(wb + (q + 1) * 512 + lane * 4);
-                    FL1 = *(const jh8*)(wb + (q + 1) * 512 + 256 + lane * 4);
-                }
-                a = __builtin_amdgcn_mfma_f32_16x16x32_f16(FL, BH[q].h(), a, 0, 0, 0);
-                a = __builtin_amdgcn_mfma_f32_16x16x32_f16(FH, BL[q].h(), a, 0, 0, 0);
-                a = __builtin_amdgcn_mfma_f32_16x16x32_f16(FH, BH[q].h(), a, 0, 0, 0);
-                __builtin_amdgcn_sched_barrier(0);
-                FH = FH1;
-                FL = FL1;
-            });
-            acc[j] = a;
-            // block J + 1 landed (this wave's pieces); the barrier publishes every wave's
-            // and retires all reads of this slot before its refill
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-            ++J;
+            acc[j] = ring_step_split<NB, WAVES>(p.wimg, wbuf, J, nblocks, BH, BL, [&] {
+                f4 a = *(const f4*)(film + layer * H + 16 * j + 4 * g);
+                if (!value) a = f4{0.f, 0.f, 0.f, 0.f};
+                return a;
+            }, wave, lane);
         });
         // acc = s_i (F_i + W_i X) in value lanes, s_i W_i T_k 2^-E_k in tangent lanes,
         // s_i W_i S_kl 2^-E_kl in second-order lanes
@@ -206,7 +177,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 8 ? 2 : 1) void siren_hess_spl
                 const float x = m * lane_value(R.src_v, av);
                 const float ak = ldexpf(lane_value(R.src_k, av), dt);
                 const float al = ldexpf(lane_value(R.src_l, av), ie);
-                const float sc = hess_sincos_role(x, !tangent);
+                const float sc = sincos_role(x, !tangent);
                 const float cu = lane_value(R.src_c, sc);
                 const float sv = second_order(w0f, w0sq, sc, cu, ldexpf(av, dh), ak, al);
                 acc[q][r] = value ? sc : tangent ? (m * sc) * av : second ? sv : 0.0f;
@@ -227,41 +198,14 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 8 ? 2 : 1) void siren_hess_spl
 
 namespace {
 
-size_t hess_split_lds(int NB, int nh) {
-    const int H = NB * 16;
-    return (size_t)(2 * NB * 256 + (nh + 1) * H + 4 * H) * sizeof(float);
-}
-
-template <int NB, int RS>
-void launch_hess_split_nb(cfd::SirenHessSplitArgs a, hipStream_t st) {
-    // K13s's workgroup: 8 waves (2 per SIMD, 256 registers each) share one weight stream
-    constexpr int WAVES = 8, TILE = (16 / RS) * WAVES;
-    const size_t lds = hess_split_lds(NB, a.nh);
-    const void* fn = (const void*)cfd::siren_hess_split<NB, RS, WAVES>;
-    CFD_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const int64_t tiles = cfd::ceil_div(a.N, TILE);
-    CFD_REQUIRE(tiles <= 0x7fffffff, CFD_EARG, "too many query points for one call");
-    for (int64_t b0 = 0; b0 < a.b; b0 += 65535) {
-        a.b0 = b0;
-        const int nb = (int)std::min<int64_t>(65535, a.b - b0);
-        hipLaunchKernelGGL((cfd::siren_hess_split<NB, RS, WAVES>), dim3((unsigned)tiles, nb), dim3(64 * WAVES), lds,
-                           st, a);
-        cfd::check_launch("siren_hess_split");
-    }
-}
-
 template <int RS>
-void launch_hess_split(int NB, const cfd::SirenHessSplitArgs& a, hipStream_t st) {
-    switch (NB) {
-        case 2: return launch_hess_split_nb<2, RS>(a, st);
-        case 4: return launch_hess_split_nb<4, RS>(a, st);
-        case 6: return launch_hess_split_nb<6, RS>(a, st);
-        case 8: return launch_hess_split_nb<8, RS>(a, st);
-        case 12: return launch_hess_split_nb<12, RS>(a, st);
-        case 16: return launch_hess_split_nb<16, RS>(a, st);
-        case 24: return launch_hess_split_nb<24, RS>(a, st);
-        default: throw cfd::Error{CFD_ESTATE, "internal: split Hessian width not checked"};
-    }
+void launch_hess_split(int nb, const cfd::SirenHessSplitArgs& a, hipStream_t st) {
+    cfd::dispatch_nb_split(nb, "internal: split Hessian width not checked", [&](auto nbc) {
+        // K13s's workgroup: 8 waves (2 per SIMD, 256 registers each) share one weight stream
+        constexpr int NB = decltype(nbc)::value, WAVES = 8;
+        cfd::launch_decode(cfd::siren_hess_split<NB, RS, WAVES>, "siren_hess_split", a, NB, (16 / RS) * WAVES, WAVES,
+                           st);
+    });
 }
 
 }  // namespace
@@ -271,56 +215,20 @@ extern "C" int cfd_siren_forward_hessian_split(cfd_siren* h, const float* coords
                                                const float* ymin, int64_t y_stride, float* out, float* jac,
                                                float* hess, int diag_only, void* ws, size_t ws_bytes, void* stream) {
     return cfd::guard([&] {
-        CFD_REQUIRE(h && coords && latents && hess, CFD_EARG, "null argument");
-        CFD_REQUIRE(N >= 1 && b >= 1, CFD_EARG, "empty decode");
-        CFD_REQUIRE((xmax == nullptr) == (xmin == nullptr), CFD_EARG, "xmax/xmin must both be set or both NULL");
-        CFD_REQUIRE((ymax == nullptr) == (ymin == nullptr), CFD_EARG, "ymax/ymin must both be set or both NULL");
-        const int d = h->cfg.in_coord_features, nh = h->cfg.num_hidden_layers, H = h->cfg.hidden_features;
-        CFD_REQUIRE(d <= 3, CFD_EARG,
-                    "cfd_siren_forward_hessian_split: in_coord_features must be 1..3 (the value, tangent and "
-                    "second-order chains of a point share 16 MFMA columns)");
-        CFD_REQUIRE(nh >= 1, CFD_EARG,
-                    "cfd_siren_forward_hessian_split: num_hidden_layers must be >= 1 (no hidden product to run on "
-                    "f16 MFMA; use cfd_siren_forward_hessian)");
-        CFD_REQUIRE(H % 32 == 0, CFD_EARG,
-                    "cfd_siren_forward_hessian_split: hidden_features must be a multiple of 32 (32-feature "
-                    "K-chunks of the f16 MFMA)");
-        CFD_REQUIRE(cfd::siren_split_supported(h->NB), CFD_EARG,
-                    "cfd_siren_forward_hessian_split: hidden_features must be 32*{1,2,3,4,6,8,12} (512 has no "
-                    "split-f16 image: its register file holds one wave per SIMD)");
-        CFD_REQUIRE(hess_split_lds(h->NB, nh) <= 160 * 1024, CFD_EARG,
-                    "cfd_siren_forward_hessian_split: SIREN too deep for the LDS staging (160 KiB)");
-        size_t need = 0;
-        cfd_siren_hessian_workspace_bytes(h, b, &need);
-        CFD_REQUIRE(ws && ws_bytes >= need, CFD_EARG, "workspace too small");
+        const char* fn = "cfd_siren_forward_hessian_split";
+        cfd::decode_check(fn, "the value, tangent and second-order chains of a point share 16 MFMA columns", h, coords,
+                          N, latents, b, xmax, xmin, ymax, ymin, hess);
+        cfd::split_refusal(fn, h);
         auto st = (hipStream_t)stream;
-        float* film = (float*)ws;
-        cfd::film_vectors(h, latents, b, film, st);
-        cfd::SirenHessSplitArgs a{};
-        a.w0 = h->w0;
+        auto a = cfd::decode_args<cfd::SirenHessSplitArgs>(h, coords, N, latents, b, xmax, xmin, ymax, ymin, y_stride,
+                                                           out, jac, ws, ws_bytes, st);
         a.wimg = h->wimg16;
         a.wscale = h->wscale;
-        a.wout = h->wout;
-        a.bout = h->bout;
-        a.film = film;
-        a.coords = coords;
-        a.xmax = xmax;
-        a.xmin = xmin;
-        a.ymax = ymax;
-        a.ymin = ymin;
-        a.out = out;
-        a.jac = jac;
         a.hess = hess;
-        a.N = N;
-        a.ystride = y_stride;
-        a.b = b;
-        a.d = d;
-        a.c = h->cfg.out_features;
-        a.nh = nh;
         a.diag = diag_only != 0;
-        a.w0f = h->cfg.w0;
         // not selected by cfd_siren_set_compute: always the split-f16 chain.  d <= 2 runs
         // the full form for both outputs; d = 3 has a diagonal form of 8 columns per point
+        const int d = a.d;
         const bool full = d < 3 || !a.diag;
         a.nsec = full ? d * (d + 1) / 2 : d;
         if (d == 1)

@@ -23,8 +23,6 @@
 // tangent columns (sincos_role, siren_jac.hpp: bit for bit sin_cw / cos_cw of common.hpp).
 // Activations and tangents never leave registers; X[NB][4] / acc[NB] are
 // siren_fused's, so is the register budget.
-#include <algorithm>
-
 #include "siren_jac.hpp"
 
 namespace cfd {
@@ -92,11 +90,7 @@ __global__ __launch_bounds__(64 * WAVES, NB <= 24 ? 2 : 1) void siren_jac_fused(
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const f4 w = *(const f4*)(w0s + 4 * (16 * q + 4 * g + r));
-            float a = cn[0] * w[0];
-#pragma unroll
-            for (int k = 1; k < 3; ++k)
-                if (k < p.d) a = fmaf(cn[k], w[k], a);
-            const float sc = sincos_role(w0f * (a + fv[r]), value);
+            const float sc = sincos_role(w0f * layer0_preact(cn, w, p.d, fv[r]), value);
             const float wk = role == 1 ? w[0] : role == 2 ? w[1] : w[2];
             X[q][r] = value ? sc : sc * (tsc * wk);
         }
@@ -183,42 +177,15 @@ __global__ __launch_bounds__(64 * WAVES, NB <= 24 ? 2 : 1) void siren_jac_fused(
 
 namespace {
 
-template <int NB, int RS>
-void launch_jac_nb(const cfd_siren* h, cfd::SirenJacArgs a, hipStream_t st) {
-    // 8 waves (2 per SIMD, 256 VGPRs each) share one weight stream; NB = 32 holds
-    // 128 + 128 registers of activations and accumulators alone, so it runs 4
-    // waves (1 per SIMD: 512 registers, the overflow in AGPRs, no scratch)
-    constexpr int WAVES = NB <= 24 ? 8 : 4, TILE = (16 / RS) * WAVES;
-    const int H = NB * 16;
-    const size_t lds = (size_t)(2 * NB * 256 + (h->cfg.num_hidden_layers + 1) * H + 4 * H) * sizeof(float);
-    const void* fn = (const void*)cfd::siren_jac_fused<NB, RS, WAVES>;
-    CFD_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const int64_t tiles = cfd::ceil_div(a.N, TILE);
-    CFD_REQUIRE(tiles <= 0x7fffffff, CFD_EARG, "too many query points for one call");
-    for (int64_t b0 = 0; b0 < a.b; b0 += 65535) {
-        a.b0 = b0;
-        const int nb = (int)std::min<int64_t>(65535, a.b - b0);
-        hipLaunchKernelGGL((cfd::siren_jac_fused<NB, RS, WAVES>), dim3((unsigned)tiles, nb), dim3(64 * WAVES), lds, st,
-                           a);
-        cfd::check_launch("siren_jac_fused");
-    }
-}
-
 template <int RS>
 void launch_jac(const cfd_siren* h, const cfd::SirenJacArgs& a, hipStream_t st) {
-    switch (h->NB) {
-        case 1: return launch_jac_nb<1, RS>(h, a, st);
-        case 2: return launch_jac_nb<2, RS>(h, a, st);
-        case 3: return launch_jac_nb<3, RS>(h, a, st);
-        case 4: return launch_jac_nb<4, RS>(h, a, st);
-        case 6: return launch_jac_nb<6, RS>(h, a, st);
-        case 8: return launch_jac_nb<8, RS>(h, a, st);
-        case 12: return launch_jac_nb<12, RS>(h, a, st);
-        case 16: return launch_jac_nb<16, RS>(h, a, st);
-        case 24: return launch_jac_nb<24, RS>(h, a, st);
-        case 32: return launch_jac_nb<32, RS>(h, a, st);
-        default: throw cfd::Error{CFD_EARG, "hidden_features must be 16*{1,2,3,4,6,8,12,16,24,32}"};
-    }
+    cfd::dispatch_nb(h->NB, [&](auto nbc) {
+        // 8 waves (2 per SIMD, 256 VGPRs each) share one weight stream; NB = 32 holds
+        // 128 + 128 registers of activations and accumulators alone, so it runs 4
+        // waves (1 per SIMD: 512 registers, the overflow in AGPRs, no scratch)
+        constexpr int NB = decltype(nbc)::value, WAVES = NB <= 24 ? 8 : 4;
+        cfd::launch_decode(cfd::siren_jac_fused<NB, RS, WAVES>, "siren_jac_fused", a, NB, (16 / RS) * WAVES, WAVES, st);
+    });
 }
 
 }  // namespace
@@ -232,42 +199,13 @@ extern "C" int cfd_siren_forward_jacobian(cfd_siren* h, const float* coords, int
                                           int64_t y_stride, float* out, float* jac, void* ws, size_t ws_bytes,
                                           void* stream) {
     return cfd::guard([&] {
-        CFD_REQUIRE(h && coords && latents && jac, CFD_EARG, "null argument");
-        CFD_REQUIRE(N >= 1 && b >= 1, CFD_EARG, "empty decode");
-        CFD_REQUIRE((xmax == nullptr) == (xmin == nullptr), CFD_EARG, "xmax/xmin must both be set or both NULL");
-        CFD_REQUIRE((ymax == nullptr) == (ymin == nullptr), CFD_EARG, "ymax/ymin must both be set or both NULL");
-        const int d = h->cfg.in_coord_features;
-        CFD_REQUIRE(d <= 3, CFD_EARG,
-                    "cfd_siren_forward_jacobian: in_coord_features must be 1..3 (the 1 + d chains of a point share "
-                    "4 MFMA columns)");
-        size_t need = 0;
-        cfd_siren_jacobian_workspace_bytes(h, b, &need);
-        CFD_REQUIRE(ws && ws_bytes >= need, CFD_EARG, "workspace too small");
+        cfd::decode_check("cfd_siren_forward_jacobian", "the 1 + d chains of a point share 4 MFMA columns", h, coords, N,
+                          latents, b, xmax, xmin, ymax, ymin, jac);
         auto st = (hipStream_t)stream;
-        float* film = (float*)ws;
-        cfd::film_vectors(h, latents, b, film, st);
-        cfd::SirenJacArgs a{};
-        a.w0 = h->w0;
-        a.wimg = h->wimg;
-        a.wout = h->wout;
-        a.bout = h->bout;
-        a.film = film;
-        a.coords = coords;
-        a.xmax = xmax;
-        a.xmin = xmin;
-        a.ymax = ymax;
-        a.ymin = ymin;
-        a.out = out;
-        a.jac = jac;
-        a.N = N;
-        a.ystride = y_stride;
-        a.b = b;
-        a.d = d;
-        a.c = h->cfg.out_features;
-        a.nh = h->cfg.num_hidden_layers;
-        a.w0f = h->cfg.w0;
+        const auto a = cfd::decode_args<cfd::SirenJacArgs>(h, coords, N, latents, b, xmax, xmin, ymax, ymin, y_stride,
+                                                           out, jac, ws, ws_bytes, st);
         // always the exact fp32 chain, whatever the handle's compute mode
-        if (d == 1)
+        if (a.d == 1)
             launch_jac<2>(h, a, st);
         else
             launch_jac<4>(h, a, st);

@@ -1,11 +1,22 @@
-// Shared pieces of the fused value-and-Jacobian decodes: K13 (siren_jac.hip, exact
-// fp32 MFMA chain) and K13s (siren_jac_split.hip, split-f16 MFMA chain).
+// Shared pieces of the SIREN derivative kernels: the fused value-and-Jacobian decodes
+// K13 (siren_jac.hip, exact fp32 MFMA chain) and K13s (siren_jac_split.hip, split-f16
+// MFMA chain), the Hessian decodes K14 / K14s (siren_hess.hpp) and the Jacobian
+// adjoints K15 / K16 (siren_jtape.hpp): device pieces first, then the host side of
+// the launches and entry points.  A device stage is here only where every kernel
+// that uses it compiles to the instructions it had with the stage written out
+// (DESIGN.md "Shared stages of the derivative kernels").
 #pragma once
+#include <algorithm>
+
 #include "siren.hpp"
 
 namespace cfd {
 
-struct SirenJacArgs {
+// What the decodes K13 / K13s / K14 / K14s read and write, grid (point tile, latent
+// row).  The kernels' argument layouts are as they were when each was tuned (moving a
+// field moves the scalar loads and with them the register allocation), so the
+// scalars that follow stay with each struct.
+struct SirenDecodeArgs {
     const float* w0;      // (H, d)
     const float* wimg;    // hidden weight image (as SirenArgs)
     const float* wout;    // (c, H)
@@ -17,7 +28,9 @@ struct SirenJacArgs {
     const float* ymax;
     const float* ymin;
     float* out;           // (b, N, c) or null
-    float* jac;           // (b, N, c, d)
+    float* jac;           // (b, N, c, d); K14 / K14s: or null
+};
+struct SirenJacArgs : SirenDecodeArgs {
     int64_t N;
     int64_t ystride;
     int64_t b0;
@@ -63,7 +76,16 @@ __device__ __forceinline__ float group_value(float v) {
     return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), ctrl, 0xF, 0xF, false));
 }
 
-// ---- range handling of the split-f16 derivative chains (K13s) ----
+// layer 0's pre-activation of one feature: cn . w + F0, w the feature's row of w0
+__device__ __forceinline__ float layer0_preact(const float (&cn)[3], const f4& w, int d, float f0) {
+    float a = cn[0] * w[0];
+#pragma unroll
+    for (int k = 1; k < 3; ++k)
+        if (k < d) a = fmaf(cn[k], w[k], a);
+    return a + f0;
+}
+
+// ---- range handling of the split-f16 derivative chains (K13s, K14s) ----
 // An MFMA column of tangents has no bound, so before its f16 split it is brought to
 // a power-of-two scale of its own.  column_exponent: from the largest magnitude m of
 // one column (the same in every lane that holds a part of it), the e with
@@ -104,6 +126,171 @@ __device__ __forceinline__ void scale_split8(const f4& x0, const f4& x1, int e, 
     hi.v = (ju4){hw[0], hw[1], hw[2], hw[3]};
     lo.v = (ju4){lw[0], lw[1], lw[2], lw[3]};
     asm volatile("" : "+v"(hi.v), "+v"(lo.v));
+}
+
+// One step of the 2-slot LDS-DMA weight ring on the split-f16 chain: issue block
+// J + 1, multiply block J (in slot J & 1) into the accumulator -- Wl xh + Wh xl + Wh xh
+// on three 16x16x32 MFMAs per K-chunk of 32 features, a block being NB / 2 chunks of
+// (hi, lo) x 512 halves -- then wait for block J + 1 (this wave's pieces); the barrier
+// publishes every wave's and retires all reads of the slot before its refill.
+// start() is the accumulator's initial value, read after the issue as the kernels
+// always did.  Chunk q + 1's A fragments are read under chunk q's MFMAs (the
+// scheduling barrier keeps the read there: left alone, the compiler reads each
+// fragment right before its use and every MFMA waits for the LDS).  Returns the
+// block's accumulator.
+template <int NB, int WAVES, class Start>
+__device__ __forceinline__ f4 ring_step_split(const float* wimg, float* wbuf, int& J, int nblocks,
+                                              const JFrag (&BH)[NB / 2], const JFrag (&BL)[NB / 2], Start&& start,
+                                              int wave, int lane) {
+    constexpr int NQ = NB / 2;
+    constexpr int BLK = NB * 256;
+    if (J + 1 < nblocks) siren_issue_block<NB, WAVES>(wimg, J + 1, wbuf + ((J + 1) & 1) * BLK, wave, lane);
+    const float* wb = wbuf + (J & 1) * BLK;
+    f4 a = start();
+    jh8 FH = *(const jh8*)(wb + lane * 4);
+    jh8 FL = *(const jh8*)(wb + 256 + lane * 4);
+    static_for<NQ>([&](auto qc) {
+        constexpr int q = decltype(qc)::value;
+        jh8 FH1 = FH, FL1 = FL;
+        if constexpr (q + 1 < NQ) {
+            FH1 = *(const jh8*)(wb + (q + 1) * 512 + lane * 4);
+            FL1 = *(const jh8*)(wb + (q + 1) * 512 + 256 + lane * 4);
+        }
+        a = __builtin_amdgcn_mfma_f32_16x16x32_f16(FL, BH[q].h(), a, 0, 0, 0);
+        a = __builtin_amdgcn_mfma_f32_16x16x32_f16(FH, BL[q].h(), a, 0, 0, 0);
+        a = __builtin_amdgcn_mfma_f32_16x16x32_f16(FH, BH[q].h(), a, 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+        FH = FH1;
+        FL = FL1;
+    });
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    ++J;
+    return a;
+}
+
+// ---- host side ----
+
+// f(std::integral_constant<int, NB>) for the widths H = 16 NB of the fp32 chain
+template <class F>
+void dispatch_nb(int NB, F&& f) {
+    switch (NB) {
+        case 1: return f(std::integral_constant<int, 1>{});
+        case 2: return f(std::integral_constant<int, 2>{});
+        case 3: return f(std::integral_constant<int, 3>{});
+        case 4: return f(std::integral_constant<int, 4>{});
+        case 6: return f(std::integral_constant<int, 6>{});
+        case 8: return f(std::integral_constant<int, 8>{});
+        case 12: return f(std::integral_constant<int, 12>{});
+        case 16: return f(std::integral_constant<int, 16>{});
+        case 24: return f(std::integral_constant<int, 24>{});
+        case 32: return f(std::integral_constant<int, 32>{});
+        default: throw Error{CFD_EARG, "hidden_features must be 16*{1,2,3,4,6,8,12,16,24,32}"};
+    }
+}
+
+// the same for the widths of the split-f16 image; split_refusal has refused the
+// others, `unchecked` is the internal error of a caller that did not ask it
+template <class F>
+void dispatch_nb_split(int NB, const char* unchecked, F&& f) {
+    switch (NB) {
+        case 2: return f(std::integral_constant<int, 2>{});
+        case 4: return f(std::integral_constant<int, 4>{});
+        case 6: return f(std::integral_constant<int, 6>{});
+        case 8: return f(std::integral_constant<int, 8>{});
+        case 12: return f(std::integral_constant<int, 12>{});
+        case 16: return f(std::integral_constant<int, 16>{});
+        case 24: return f(std::integral_constant<int, 24>{});
+        default: throw Error{CFD_ESTATE, unchecked};
+    }
+}
+
+// LDS of a decode: 2 ring slots, the FiLM rows (nh+1, H), w0 as (H, 4)
+inline size_t deriv_lds(int NB, int nh) {
+    const int H = NB * 16;
+    return (size_t)(2 * NB * 256 + (nh + 1) * H + 4 * H) * sizeof(float);
+}
+
+// A decode kernel of width H = 16 NB on its grid (tile of `tile` points, latent row),
+// the rows in slabs of 65535
+template <class Args>
+void launch_decode(void (*kernel)(Args), const char* name, Args a, int NB, int tile, int waves, hipStream_t st) {
+    const size_t lds = deriv_lds(NB, a.nh);
+    CFD_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const int64_t tiles = ceil_div(a.N, tile);
+    CFD_REQUIRE(tiles <= 0x7fffffff, CFD_EARG, "too many query points for one call");
+    for (int64_t b0 = 0; b0 < a.b; b0 += 65535) {
+        a.b0 = b0;
+        const int nb = (int)std::min<int64_t>(65535, a.b - b0);
+        hipLaunchKernelGGL(kernel, dim3((unsigned)tiles, nb), dim3(64 * waves), lds, st, a);
+        check_launch(name);
+    }
+}
+
+// the fields every kernel of the family takes from the handle
+template <class Args>
+void handle_args(Args& a, const cfd_siren* h) {
+    a.w0 = h->w0;
+    a.wimg = h->wimg;
+    a.wout = h->wout;
+    a.bout = h->bout;
+    a.d = h->cfg.in_coord_features;
+    a.c = h->cfg.out_features;
+    a.nh = h->cfg.num_hidden_layers;
+    a.w0f = h->cfg.w0;
+}
+
+// What the four decode entry points (`fn`) check first; `result` is the output that
+// must not be null, `columns` why d is bounded.
+inline void decode_check(const char* fn, const char* columns, const cfd_siren* h, const float* coords, int64_t N,
+                         const float* latents, int b, const float* xmax, const float* xmin, const float* ymax,
+                         const float* ymin, const float* result) {
+    CFD_REQUIRE(h && coords && latents && result, CFD_EARG, "null argument");
+    CFD_REQUIRE(N >= 1 && b >= 1, CFD_EARG, "empty decode");
+    CFD_REQUIRE((xmax == nullptr) == (xmin == nullptr), CFD_EARG, "xmax/xmin must both be set or both NULL");
+    CFD_REQUIRE((ymax == nullptr) == (ymin == nullptr), CFD_EARG, "ymax/ymin must both be set or both NULL");
+    CFD_REQUIRE(h->cfg.in_coord_features <= 3, CFD_EARG,
+                std::string(fn) + ": in_coord_features must be 1..3 (" + columns + ")");
+}
+
+// What the split-f16 entry point `fn` ("..._split") refuses, after decode_check
+inline void split_refusal(const std::string& fn, const cfd_siren* h) {
+    const int nh = h->cfg.num_hidden_layers;
+    CFD_REQUIRE(nh >= 1, CFD_EARG,
+                fn + ": num_hidden_layers must be >= 1 (no hidden product to run on f16 MFMA; use " +
+                    fn.substr(0, fn.size() - 6) + ")");
+    CFD_REQUIRE(h->cfg.hidden_features % 32 == 0, CFD_EARG,
+                fn + ": hidden_features must be a multiple of 32 (32-feature K-chunks of the f16 MFMA)");
+    CFD_REQUIRE(siren_split_supported(h->NB), CFD_EARG,
+                fn + ": hidden_features must be 32*{1,2,3,4,6,8,12} (512 has no split-f16 image: its register file "
+                     "holds one wave per SIMD)");
+    CFD_REQUIRE(deriv_lds(h->NB, nh) <= 160 * 1024, CFD_EARG, fn + ": SIREN too deep for the LDS staging (160 KiB)");
+}
+
+// The rest of a decode entry point: the workspace check, the FiLM vectors (b, nh+1, H)
+// into the workspace, and the launch arguments (out may be null).
+template <class Args>
+Args decode_args(const cfd_siren* h, const float* coords, int64_t N, const float* latents, int b, const float* xmax,
+                 const float* xmin, const float* ymax, const float* ymin, int64_t y_stride, float* out, float* jac,
+                 void* ws, size_t ws_bytes, hipStream_t st) {
+    size_t need = 0;
+    cfd_siren_workspace_bytes(h, b, &need);
+    CFD_REQUIRE(ws && ws_bytes >= need, CFD_EARG, "workspace too small");
+    cfd::film_vectors(h, latents, b, (float*)ws, st);
+    Args a{};
+    handle_args(a, h);
+    a.film = (const float*)ws;
+    a.coords = coords;
+    a.xmax = xmax;
+    a.xmin = xmin;
+    a.ymax = ymax;
+    a.ymin = ymin;
+    a.out = out;
+    a.jac = jac;
+    a.N = N;
+    a.ystride = y_stride;
+    a.b = b;
+    return a;
 }
 
 }  // namespace cfd

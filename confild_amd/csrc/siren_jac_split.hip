@@ -26,8 +26,6 @@
 // coordinates by a power of two scales the Jacobian by exactly its inverse.  Value
 // columns take exponent 0 (K7s's split).  An all-zero column (the idle column at
 // d = 2, a tangent that is identically 0) takes exponent 0 and stays 0.
-#include <algorithm>
-
 #include "siren_jac.hpp"
 
 namespace cfd {
@@ -121,11 +119,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void siren_jac_split(SirenJacSplitAr
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const f4 w = *(const f4*)(w0s + 4 * (16 * q + 4 * g + r));
-            float a = cn[0] * w[0];
-#pragma unroll
-            for (int k = 1; k < 3; ++k)
-                if (k < p.d) a = fmaf(cn[k], w[k], a);
-            const float sc = sincos_role(w0f * (a + fv[r]), value);
+            const float sc = sincos_role(w0f * layer0_preact(cn, w, p.d, fv[r]), value);
             const float wk = role == 1 ? w[0] : role == 2 ? w[1] : w[2];
             acc[q][r] = value ? sc : sc * (tsc * wk);
         }
@@ -142,35 +136,11 @@ __global__ __launch_bounds__(64 * WAVES, 2) void siren_jac_split(SirenJacSplitAr
         const float m = w0f / p.wscale[layer - 1];  // power-of-two scale: exact
         static_for<NB>([&](auto jc) {
             constexpr int j = decltype(jc)::value;
-            if (J + 1 < nblocks) siren_issue_block<NB, WAVES>(p.wimg, J + 1, wbuf + ((J + 1) & 1) * BLK, wave, lane);
-            const float* wb = wbuf + (J & 1) * BLK;
-            f4 a = *(const f4*)(film + layer * H + 16 * j + 4 * g);
-            if (!value) a = f4{0.f, 0.f, 0.f, 0.f};
-            // chunk q + 1's A fragments are read under chunk q's MFMAs (the scheduling
-            // barrier keeps the read there: left alone, the compiler reads each
-            // fragment right before its use and every MFMA waits for the LDS)
-            jh8 FH = *(const jh8*)(wb + lane * 4);
-            jh8 FL = *(const jh8*)(wb + 256 + lane * 4);
-            static_for<NQ>([&](auto qc) {
-                constexpr int q = decltype(qc)::value;
-                jh8 FH1 = FH, FL1 = FL;
-                if constexpr (q + 1 < NQ) {
-                    FH1 = *(const jh8*)(wb + (q + 1) * 512 + lane * 4);
-                    FL1 = *(const jh8*)(wb + (q + 1) * 512 + 256 + lane * 4);
-                }
-                a = __builtin_amdgcn_mfma_f32_16x16x32_f16(FL, BH[q].h(), a, 0, 0, 0);
-                a = __builtin_amdgcn_mfma_f32_16x16x32_f16(FH, BL[q].h(), a, 0, 0, 0);
-                a = __builtin_amdgcn_mfma_f32_16x16x32_f16(FH, BH[q].h(), a, 0, 0, 0);
-                __builtin_amdgcn_sched_barrier(0);
-                FH = FH1;
-                FL = FL1;
-            });
-            acc[j] = a;
-            // block J + 1 landed (this wave's pieces); the barrier publishes every wave's
-            // and retires all reads of this slot before its refill
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-            ++J;
+            acc[j] = ring_step_split<NB, WAVES>(p.wimg, wbuf, J, nblocks, BH, BL, [&] {
+                f4 a = *(const f4*)(film + layer * H + 16 * j + 4 * g);
+                if (!value) a = f4{0.f, 0.f, 0.f, 0.f};
+                return a;
+            }, wave, lane);
         });
         // acc = s_i (F_i + W_i X) in value lanes, s_i W_i T 2^-E in tangent lanes
         static_for<NB>([&](auto qc) {
@@ -232,40 +202,13 @@ namespace {
 
 constexpr int JS_WAVES = 8;   // 2 per SIMD, 256 registers each, sharing one weight stream
 
-size_t jac_split_lds(int NB, int nh) {
-    const int H = NB * 16;
-    return (size_t)(2 * NB * 256 + (nh + 1) * H + 4 * H) * sizeof(float);
-}
-
-template <int NB, int RS>
-void launch_jac_split_nb(cfd::SirenJacSplitArgs a, hipStream_t st) {
-    constexpr int TILE = (16 / RS) * JS_WAVES;
-    const size_t lds = jac_split_lds(NB, a.nh);
-    const void* fn = (const void*)cfd::siren_jac_split<NB, RS, JS_WAVES>;
-    CFD_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const int64_t tiles = cfd::ceil_div(a.N, TILE);
-    CFD_REQUIRE(tiles <= 0x7fffffff, CFD_EARG, "too many query points for one call");
-    for (int64_t b0 = 0; b0 < a.b; b0 += 65535) {
-        a.b0 = b0;
-        const int nb = (int)std::min<int64_t>(65535, a.b - b0);
-        hipLaunchKernelGGL((cfd::siren_jac_split<NB, RS, JS_WAVES>), dim3((unsigned)tiles, nb), dim3(64 * JS_WAVES),
-                           lds, st, a);
-        cfd::check_launch("siren_jac_split");
-    }
-}
-
 template <int RS>
-void launch_jac_split(int NB, const cfd::SirenJacSplitArgs& a, hipStream_t st) {
-    switch (NB) {
-        case 2: return launch_jac_split_nb<2, RS>(a, st);
-        case 4: return launch_jac_split_nb<4, RS>(a, st);
-        case 6: return launch_jac_split_nb<6, RS>(a, st);
-        case 8: return launch_jac_split_nb<8, RS>(a, st);
-        case 12: return launch_jac_split_nb<12, RS>(a, st);
-        case 16: return launch_jac_split_nb<16, RS>(a, st);
-        case 24: return launch_jac_split_nb<24, RS>(a, st);
-        default: throw cfd::Error{CFD_ESTATE, "internal: split Jacobian width not checked"};
-    }
+void launch_jac_split(int nb, const cfd::SirenJacSplitArgs& a, hipStream_t st) {
+    cfd::dispatch_nb_split(nb, "internal: split Jacobian width not checked", [&](auto nbc) {
+        constexpr int NB = decltype(nbc)::value;
+        cfd::launch_decode(cfd::siren_jac_split<NB, RS, JS_WAVES>, "siren_jac_split", a, NB, (16 / RS) * JS_WAVES,
+                           JS_WAVES, st);
+    });
 }
 
 }  // namespace
@@ -275,53 +218,16 @@ extern "C" int cfd_siren_forward_jacobian_split(cfd_siren* h, const float* coord
                                                 const float* ymin, int64_t y_stride, float* out, float* jac, void* ws,
                                                 size_t ws_bytes, void* stream) {
     return cfd::guard([&] {
-        CFD_REQUIRE(h && coords && latents && jac, CFD_EARG, "null argument");
-        CFD_REQUIRE(N >= 1 && b >= 1, CFD_EARG, "empty decode");
-        CFD_REQUIRE((xmax == nullptr) == (xmin == nullptr), CFD_EARG, "xmax/xmin must both be set or both NULL");
-        CFD_REQUIRE((ymax == nullptr) == (ymin == nullptr), CFD_EARG, "ymax/ymin must both be set or both NULL");
-        const int d = h->cfg.in_coord_features, nh = h->cfg.num_hidden_layers, H = h->cfg.hidden_features;
-        CFD_REQUIRE(d <= 3, CFD_EARG,
-                    "cfd_siren_forward_jacobian_split: in_coord_features must be 1..3 (the 1 + d chains of a point "
-                    "share 4 MFMA columns)");
-        CFD_REQUIRE(nh >= 1, CFD_EARG,
-                    "cfd_siren_forward_jacobian_split: num_hidden_layers must be >= 1 (no hidden product to run on "
-                    "f16 MFMA; use cfd_siren_forward_jacobian)");
-        CFD_REQUIRE(H % 32 == 0, CFD_EARG,
-                    "cfd_siren_forward_jacobian_split: hidden_features must be a multiple of 32 (32-feature "
-                    "K-chunks of the f16 MFMA)");
-        CFD_REQUIRE(cfd::siren_split_supported(h->NB), CFD_EARG,
-                    "cfd_siren_forward_jacobian_split: hidden_features must be 32*{1,2,3,4,6,8,12} (512 has no "
-                    "split-f16 image: its register file holds one wave per SIMD)");
-        CFD_REQUIRE(jac_split_lds(h->NB, nh) <= 160 * 1024, CFD_EARG,
-                    "cfd_siren_forward_jacobian_split: SIREN too deep for the LDS staging (160 KiB)");
-        size_t need = 0;
-        cfd_siren_jacobian_workspace_bytes(h, b, &need);
-        CFD_REQUIRE(ws && ws_bytes >= need, CFD_EARG, "workspace too small");
+        const char* fn = "cfd_siren_forward_jacobian_split";
+        cfd::decode_check(fn, "the 1 + d chains of a point share 4 MFMA columns", h, coords, N, latents, b, xmax, xmin,
+                          ymax, ymin, jac);
+        cfd::split_refusal(fn, h);
         auto st = (hipStream_t)stream;
-        float* film = (float*)ws;
-        cfd::film_vectors(h, latents, b, film, st);
-        cfd::SirenJacSplitArgs a{};
-        a.w0 = h->w0;
+        auto a = cfd::decode_args<cfd::SirenJacSplitArgs>(h, coords, N, latents, b, xmax, xmin, ymax, ymin, y_stride,
+                                                          out, jac, ws, ws_bytes, st);
         a.wimg = h->wimg16;
         a.wscale = h->wscale;
-        a.wout = h->wout;
-        a.bout = h->bout;
-        a.film = film;
-        a.coords = coords;
-        a.xmax = xmax;
-        a.xmin = xmin;
-        a.ymax = ymax;
-        a.ymin = ymin;
-        a.out = out;
-        a.jac = jac;
-        a.N = N;
-        a.ystride = y_stride;
-        a.b = b;
-        a.d = d;
-        a.c = h->cfg.out_features;
-        a.nh = nh;
-        a.w0f = h->cfg.w0;
-        if (d == 1)
+        if (a.d == 1)
             launch_jac_split<2>(h->NB, a, st);
         else
             launch_jac_split<4>(h->NB, a, st);

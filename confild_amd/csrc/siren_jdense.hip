@@ -216,20 +216,8 @@ void launch_jdense_nb(const SirenJDenseArgs& a, int rows, bool bwd, hipStream_t 
 }
 
 template <int RS>
-void launch_jdense(int NB, const SirenJDenseArgs& a, int rows, bool bwd, hipStream_t st) {
-    switch (NB) {
-        case 1: return launch_jdense_nb<1, RS>(a, rows, bwd, st);
-        case 2: return launch_jdense_nb<2, RS>(a, rows, bwd, st);
-        case 3: return launch_jdense_nb<3, RS>(a, rows, bwd, st);
-        case 4: return launch_jdense_nb<4, RS>(a, rows, bwd, st);
-        case 6: return launch_jdense_nb<6, RS>(a, rows, bwd, st);
-        case 8: return launch_jdense_nb<8, RS>(a, rows, bwd, st);
-        case 12: return launch_jdense_nb<12, RS>(a, rows, bwd, st);
-        case 16: return launch_jdense_nb<16, RS>(a, rows, bwd, st);
-        case 24: return launch_jdense_nb<24, RS>(a, rows, bwd, st);
-        case 32: return launch_jdense_nb<32, RS>(a, rows, bwd, st);
-        default: throw Error{CFD_EARG, "hidden_features must be 16*{1,2,3,4,6,8,12,16,24,32}"};
-    }
+void launch_jdense(int nb, const SirenJDenseArgs& a, int rows, bool bwd, hipStream_t st) {
+    dispatch_nb(nb, [&](auto nbc) { launch_jdense_nb<decltype(nbc)::value, RS>(a, rows, bwd, st); });
 }
 
 }  // namespace
@@ -300,11 +288,8 @@ extern "C" int cfd_siren_jdense_grad(cfd_siren* h, const float* coords, int64_t 
                 const int slabs = (int)cfd::ceil_div(nc, cfd::kJSlab);
                 const int tiles = (int)cfd::ceil_div(nc, tile);
                 cfd::SirenJDenseArgs a{};
-                a.w0 = h->w0;
-                a.wimg = h->wimg;
+                cfd::handle_args(a, h);
                 a.wimg_t = h->wimg_t;
-                a.wout = h->wout;
-                a.bout = h->bout;
                 a.film = film + (int64_t)r0 * nf;
                 a.coords = coords + n0 * d;
                 a.xmax = xmax;
@@ -320,10 +305,6 @@ extern "C" int cfd_siren_jdense_grad(cfd_siren* h, const float* coords, int64_t 
                 a.part = base + pl.tiles;
                 a.P = (int64_t)rows * nc;
                 a.Ns = nc;
-                a.d = d;
-                a.c = c;
-                a.nh = nh;
-                a.w0f = h->cfg.w0;
                 if (d == 1) cfd::launch_jdense<2>(h->NB, a, rows, false, st);
                 else cfd::launch_jdense<4>(h->NB, a, rows, false, st);
                 hipLaunchKernelGGL(cfd::jdense_residual_kernel, dim3(slabs, rows), dim3(cfd::kJSlab), 0, st,

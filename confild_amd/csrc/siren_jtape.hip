@@ -26,19 +26,7 @@ void launch_jtape_nb(const cfd::SirenJTapeArgs& a, bool bwd, hipStream_t st) {
 
 template <int RS>
 void launch_jtape(const cfd_siren* h, const cfd::SirenJTapeArgs& a, bool bwd, hipStream_t st) {
-    switch (h->NB) {
-        case 1: return launch_jtape_nb<1, RS>(a, bwd, st);
-        case 2: return launch_jtape_nb<2, RS>(a, bwd, st);
-        case 3: return launch_jtape_nb<3, RS>(a, bwd, st);
-        case 4: return launch_jtape_nb<4, RS>(a, bwd, st);
-        case 6: return launch_jtape_nb<6, RS>(a, bwd, st);
-        case 8: return launch_jtape_nb<8, RS>(a, bwd, st);
-        case 12: return launch_jtape_nb<12, RS>(a, bwd, st);
-        case 16: return launch_jtape_nb<16, RS>(a, bwd, st);
-        case 24: return launch_jtape_nb<24, RS>(a, bwd, st);
-        case 32: return launch_jtape_nb<32, RS>(a, bwd, st);
-        default: throw cfd::Error{CFD_EARG, "hidden_features must be 16*{1,2,3,4,6,8,12,16,24,32}"};
-    }
+    cfd::dispatch_nb(h->NB, [&](auto nbc) { launch_jtape_nb<decltype(nbc)::value, RS>(a, bwd, st); });
 }
 
 // every shape check of the pair, before any launch
@@ -66,20 +54,13 @@ JTapeWs jtape_ws(const cfd_siren* h, int64_t Ns, int R, void* ws) {
 }
 
 void jtape_args(const cfd_siren* h, cfd::SirenJTapeArgs& a, const JTapeWs& w, int64_t Ns, int R) {
-    a.w0 = h->w0;
-    a.wimg = h->wimg;
+    cfd::handle_args(a, h);
     a.wimg_t = h->wimg_t;
-    a.wout = h->wout;
-    a.bout = h->bout;
     a.film = w.film;
     a.tape = w.tape;
     a.delta = w.delta;
     a.P = (int64_t)R * Ns;
     a.Ns = (int)Ns;
-    a.d = h->cfg.in_coord_features;
-    a.c = h->cfg.out_features;
-    a.nh = h->cfg.num_hidden_layers;
-    a.w0f = h->cfg.w0;
 }
 
 }  // namespace

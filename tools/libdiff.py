@@ -20,6 +20,12 @@ shapes are "up/" cases already): a build with K1h on another MFMA shape (16x16x3
 against 32x32x16, make VARIANT=k1h32 VFLAGS=-DCFD_K1H_MFMA32) is expected to differ
 there at rounding level, in the forward and in what is computed from its tape, and
 is held to the same tolerance.  Every other case must be bit-identical.
+
+The cases named "deriv/..." are the SIREN derivative kernels (K13, K13s, K14, K14s,
+K15, K16), every output hashed, with and without the normalisers; `--deriv` runs only
+these (a few seconds):
+
+    python tools/libdiff.py libconfild_hip_pre.so libconfild_hip.so --deriv
 """
 from __future__ import annotations
 
@@ -42,6 +48,67 @@ from confild_amd.nf_networks import SIRENAutodecoder_film
 out = {}
 def h(t):
     return hashlib.sha256(t.detach().cpu().contiguous().numpy().tobytes()).hexdigest()[:16]
+DERIV_ONLY = len(sys.argv) > 3 and sys.argv[3] == "deriv"
+def emit():
+    np.savez(sys.argv[2], **{k.replace("/", "|"): v for k, v in vals.items()})
+    print(json.dumps(out))
+# The SIREN derivative kernels, 77 points and 2 latent rows, each network the smallest
+# that reaches a distinct instantiation; every case with both normalisers and with neither.
+from confild_amd.normalize import Normalizer_ts
+def siren(dims):
+    nf = SIRENAutodecoder_film(*dims)
+    nf.load_state_dict({k: torch.from_numpy(v) for k, v in synth.siren_state_dict(5, *dims).items()})
+    return nf.to("cuda")
+def normalisers(dims, N, tag):
+    d, c = dims[0], dims[2]
+    xn = Normalizer_ts(params=(torch.from_numpy(synth.uniform(6, tag + "/xmax", (1, d), 1.5, 2.0)),
+                               torch.from_numpy(synth.uniform(6, tag + "/xmin", (1, d), -0.5, -0.2))), method="-11", dim=0)
+    yn = Normalizer_ts(params=(torch.from_numpy(synth.uniform(6, tag + "/ymax", (1, N, c), 0.5, 2.0)),
+                               torch.from_numpy(synth.uniform(6, tag + "/ymin", (1, N, c), -2.0, -0.5))), method="-11", dim=0)
+    return {"norm": (xn, yn), "raw": (None, None)}
+F32 = ((1, 8, 1, 2, 16), (2, 8, 2, 3, 48), (3, 8, 3, 2, 512), (3, 64, 3, 15, 384))
+SPLIT = ((1, 8, 1, 1, 32), (2, 8, 4, 1, 32), (2, 128, 2, 17, 256), (3, 64, 3, 15, 384))
+for dims in sorted(set(F32 + SPLIT)):
+    nf = siren(dims)
+    g = torch.Generator().manual_seed(3)
+    coords = torch.rand(77, dims[0], generator=g).cuda()
+    lat = (torch.randn(2, 1, dims[1], generator=g) * 0.5).cuda()
+    for nk, (xn, yn) in normalisers(dims, 77, "ld/deriv").items():
+        if dims in F32:   # K13
+            o, j = nf.decode_jacobian(coords, lat, xn, yn)
+            out[f"deriv/jacobian/{dims}/{nk}"] = h(o) + h(j)
+        if dims in F32 or dims == (2, 128, 2, 17, 256):   # K14: full and diagonal form
+            for diag in (False, True):
+                o, j, hs = nf.decode_hessian(coords, lat, xn, yn, diag=diag)
+                out[f"deriv/hessian/{dims}/{'diag' if diag else 'full'}/{nk}"] = h(o) + h(j) + h(hs)
+        if dims in SPLIT:   # K13s, K14s
+            o, j = nf.decode_jacobian(coords, lat, xn, yn, compute="split_f16")
+            out[f"deriv/jacobian_split/{dims}/{nk}"] = h(o) + h(j)
+            for diag in (False, True):
+                o, j, hs = nf.decode_hessian(coords, lat, xn, yn, diag=diag, compute="split_f16")
+                out[f"deriv/hessian_split/{dims}/{'diag' if diag else 'full'}/{nk}"] = h(o) + h(j) + h(hs)
+    if dims in F32:   # K15: 5 sensors, 3 rows
+        sens = torch.rand(5, dims[0], generator=g).cuda()
+        rows = (torch.randn(3, dims[1], generator=g) * 0.5).cuda()
+        for nk, (xn, yn) in normalisers(dims, 5, "ld/jvjp").items():
+            o, j = nf.jac_tape_forward(sens, rows, xn, yn)
+            gz = nf.jac_tape_vjp(torch.randn(o.shape, generator=g).cuda(), torch.randn(j.shape, generator=g).cuda())
+            out[f"deriv/jvjp/{dims}/{nk}"] = h(o) + h(j) + h(gz)
+# K16: two 64-point slabs with a short last one (the shapes of tests/test_gpu_siren_jdense.py);
+# the first has no hidden layer, so the second adds the weight ring
+for dims, N, R, T in (((3, 16, 1, 0, 64), 65, 2, 1), ((2, 128, 2, 2, 256), 70, 3, 3)):
+    nf = siren(dims)
+    d, c = dims[0], dims[2]
+    g = torch.Generator().manual_seed(4)
+    coords = torch.rand(N, d, generator=g).cuda()
+    lat = (torch.randn(R, dims[1], generator=g) * 0.5).cuda()
+    y, wv, wj = torch.randn(T, N, 3, generator=g).cuda(), torch.randn(N, 3, c, generator=g).cuda(), (torch.randn(3, c, d, generator=g) * 0.3).cuda()
+    for nk, (xn, yn) in normalisers(dims, N, "ld/jdense").items():
+        gz, norms = nf.jac_dense_grad(coords, lat, T, y, wv, wj, None, xn, yn)
+        out[f"deriv/jdense/{dims}/N{N}/{nk}"] = h(gz) + h(norms)
+if DERIV_ONLY:
+    emit()
+    sys.exit(0)
 cases = [(16, "2", "split_f16", (3,)), (32, "3", "split_f16", (1,)), (32, "1,2,3,4", "split_f16", (1, 3)), (64, "", "split_f16", (1, 2, 8)), (128, "", "bf16", (2,)),
          (64, "", "fp32", (2,)), (128, "", "split_f16", (1,)), (384, "1,1,2,2,4,4", "split_f16", (1,))]
 for S, mult, comp, Bs in cases:
@@ -96,17 +163,6 @@ for dims in ((3, 8, 3, 1, 64), (3, 16, 3, 1, 128), (2, 16, 2, 1, 256), (3, 16, 3
     coords = torch.rand(385, dims[0], generator=g).cuda()
     lat = (torch.randn(3, 1, dims[1], generator=g) * 0.5).cuda()
     out[f"siren_ring/{dims}"] = h(nf(coords, lat))
-# the fused value-Jacobian-Hessian decode (K14): d = 1..3, full and diagonal form, odd NB, H = 512
-for dims in ((1, 8, 1, 2, 16), (2, 8, 2, 3, 48), (2, 128, 2, 17, 256), (3, 64, 3, 15, 384), (3, 8, 3, 2, 512)):
-    nf = SIRENAutodecoder_film(*dims)
-    nf.load_state_dict({k: torch.from_numpy(v) for k, v in synth.siren_state_dict(5, *dims).items()})
-    nf.to("cuda")
-    g = torch.Generator().manual_seed(3)
-    coords = torch.rand(77, dims[0], generator=g).cuda()
-    lat = (torch.randn(2, 1, dims[1], generator=g) * 0.5).cuda()
-    for diag in (False, True):
-        o, j, hs = nf.decode_hessian(coords, lat, diag=diag)
-        out[f"siren_hessian/{dims}/{'diag' if diag else 'full'}"] = h(o) + h(j) + h(hs)
 # one Upsample convolution on its own (builds that have the entry point)
 from confild_amd import _lib
 import ctypes as C
@@ -121,15 +177,14 @@ if hasattr(_lib.lib(), "cfd_upsample_conv"):
                                                 _lib.ptr(o), B, H, W, Ci, Co, 0, 0, C.byref(kx), None), "upconv")
         out[f"up/conv/{B}x{H}x{W}x{Ci}"] = h(o)
         vals[f"up/conv/{B}x{H}x{W}x{Ci}"] = o.cpu().numpy()
-np.savez(sys.argv[2], **{k.replace("/", "|"): v for k, v in vals.items()})
-print(json.dumps(out))
+emit()
 """
 
 
-def run(lib, tmp):
+def run(lib, tmp, only):
     env = dict(os.environ, CFD_LIB=lib)
     vals = os.path.join(tmp, os.path.basename(lib) + ".npz")
-    r = subprocess.run([sys.executable, "-c", CHILD, ROOT, vals], capture_output=True, text=True, env=env,
+    r = subprocess.run([sys.executable, "-c", CHILD, ROOT, vals, only], capture_output=True, text=True, env=env,
                        timeout=900)
     if r.returncode != 0:
         print(r.stderr[-3000:])
@@ -143,8 +198,9 @@ if __name__ == "__main__":
     import numpy as np
 
     a, b = sys.argv[1], sys.argv[2]
+    only = "deriv" if "--deriv" in sys.argv[3:] else "all"
     with tempfile.TemporaryDirectory() as tmp:
-        (ra, va), (rb, vb) = run(a, tmp), run(b, tmp)
+        (ra, va), (rb, vb) = run(a, tmp, only), run(b, tmp, only)
         both = [k for k in ra if k in rb]
         diff = [k for k in both if ra[k] != rb[k]]
         za, zb = np.load(va), np.load(vb)
@@ -155,7 +211,7 @@ if __name__ == "__main__":
                 rel[k] = float(np.abs(za[f].astype(np.float64) - zb[f]).max() / np.abs(za[f]).max())
     bad = [k for k in diff if not k.startswith(ROUNDING)]
     beyond = [k for k, v in rel.items() if not v <= UP_TOL]
-    print(json.dumps({"a": a, "b": b, "cases": len(both), "only_in_one": sorted(set(ra) ^ set(rb)),
+    print(json.dumps({"a": a, "b": b, "cases": len(both), "deriv_cases": len([k for k in both if k.startswith("deriv/")]), "only_in_one": sorted(set(ra) ^ set(rb)),
                       "differ_upsample": {k: rel.get(k) for k in diff if k.startswith("up/")},
                       "differ_k1h": {k: rel.get(k) for k in diff if k.startswith("k1h/")},
                       "unbounded": [k for k in diff if k.startswith(ROUNDING) and k not in rel],
